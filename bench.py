@@ -13,9 +13,11 @@ evaluation, three-level WBC) over a batch of 256 independent AlienGo+Z1 instance
              (torch.distributed.run on 127.0.0.1).
 Inputs are resident in HBM before the timed region.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (HIP events on the kernels' own stream, recorded during
-the timed steps); `cpu_baseline` times the CPU oracle (a restatement, NOT the reference OCS2 path, which cannot be built here)
-on a bounded sample, rank 0 at N = 1 only.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps and prints the headline (value, ms_per_step, ...);
+--dump-outputs DIR also writes what the timed path computed in its last step to DIR/<name>.npy.  --full adds everything else after the timed
+steps: the result checks, `roofline` for the dominant kernel (HIP events on the kernels' own stream, recorded during the timed steps, and a
+one-stream calibration pass), config.steady_state, config.batch_sweep (--sweep) and `cpu_baseline`, which times the CPU oracle (a restatement,
+NOT the reference OCS2 path, which cannot be built here) on a bounded sample, rank 0 at N = 1 only.
 """
 import argparse
 import json
@@ -283,6 +285,73 @@ def profile_counters():
         return None, {}
 
 
+def roofline(res, kernel_ms, kernel_ms_serial, calibration_same, ms_per_step, N, emulate):
+    """--full: the roofline block of the line for the dominant kernel (the one-stream durations of the calibration pass when the overlap is on)"""
+    names = ["ad_node_kernel", "lq_node_kernel", "riccati_kernel", "linesearch_kernel", "wbc_kernel"]
+    modes = res["mode"][:, :N]
+    nst = np.array([[bin(int(m)).count("1") for m in row] for row in modes])
+    nc = 3 * nst + 4 * (4 - nst)
+    flops = {k: 0.0 for k in ("ad_node_kernel", "lq_node_kernel", "riccati_kernel")}
+    for v in np.unique(nc):
+        cnt = int((nc == v).sum())
+        for k, f in node_flops(int(v)).items():
+            flops[k] += cnt * f
+    dom_name = max(flops, key=lambda k: kernel_ms_serial[names.index(k)])   # longest launch (device to itself) among the kernels that carry algorithmic FLOPs
+    path_flops = flops["ad_node_kernel"] + flops["lq_node_kernel"] + flops["riccati_kernel"]
+    roof_kernel = dom_name
+    tf = lambda fl, ms: (fl / (ms * 1e-3) / 1e12) if ms > 0 else None   # noqa: E731  (the emulation has no clocks)
+    # ONE source for the roofline block: the kernel, its duration, achieved / frac, kernel_frac and hbm_gbps all come from the one-stream durations (the calibration pass
+    # when the overlap is on, the timed region itself otherwise); the timed region's own interval of the same kernel is reported next to it
+    achieved = tf(flops[roof_kernel], kernel_ms_serial[names.index(roof_kernel)])
+    achieved_timed = tf(flops[roof_kernel], kernel_ms[names.index(roof_kernel)])
+    tag, ctr = profile_counters()
+    traffic = ctr.get(roof_kernel, {}).get("bytes")
+    src = (f"profiles/{tag}_counters.json (separate rocprofv3 --pmc passes of `bench.py --no-cpu-baseline --no-overlap --steps 5`, summarised by tools/make_profile_summaries.py; "
+           "NOT measured in this run)") if tag else "no committed counter set"
+    # HBM GB/s and matrix-core busy per kernel: counter values per launch (committed profile) over THIS run's HIP-event launch times
+    hbm = {k: (ctr[k]["bytes"] / (kernel_ms_serial[names.index(k)] * 1e-3) / 1e9) for k in names if k in ctr and kernel_ms_serial[names.index(k)] > 0}
+    busy = {k: ctr[k]["mfma_busy"] for k in names if k in ctr and "mfma_busy" in ctr[k]}
+    return {"bound": "mfma", "kernel": roof_kernel, "achieved": achieved, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": (achieved / FP64_MFMA_PEAK_TFLOPS) if achieved is not None else None,
+            "achieved_from_the_timed_regions_interval": achieved_timed, "calibration_pass_reproduces_the_timed_results": calibration_same,
+            "traffic": traffic, "traffic_source": src,
+            "mfma_busy": busy.get(roof_kernel), "hbm_gbps": hbm.get(roof_kernel),
+            "mfma_busy_by_kernel": busy, "hbm_gbps_by_kernel": hbm,
+            "hbm_bytes_per_step": sum(v["bytes"] for k, v in ctr.items() if isinstance(v, dict) and "bytes" in v) or None,
+            "counters_note": "mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (launch duration x 2.4 GHz x 1024 SIMDs) of the committed PMC pass; hbm_gbps = committed "
+                             "(2 x FETCH_SIZE + WRITE_SIZE) bytes per launch / this run's HIP-event launch time; HBM peak 8000 GB/s spec, 6290 GB/s measured copy rate",
+            "note": "algorithmic dense-contraction FLOPs of SURVEY.md 8(d) per launch / HIP-event kernel time; fp64 matrix peak is the public spec; "
+                    "the path is latency bound, not MFMA bound (DESIGN.md)",
+            "kernel_ms": dict(zip(names + ["whole_call"], kernel_ms)),
+            "kernel_ms_one_stream": dict(zip(names + ["whole_call"], kernel_ms_serial)),
+            "kernel_ms_note": "kernel_ms: HIP events over the TIMED region (with the overlap on, ad_node's interval includes its wait for the CUs the previous step's WBC still holds, and whole_call spans two "
+                              "streams); kernel_ms_one_stream: the same cycle on one stream in a calibration pass after the timed region (outside `value`): what `kernel`, kernel_frac and hbm_gbps are computed "
+                              "from, `achieved` / `frac` included (achieved_from_the_timed_regions_interval: the same FLOPs over the timed region's own interval of that kernel)",
+            # launches within 5 % of the longest one: since round 3 the three FLOP-carrying kernels take 0.45-0.47 ms each, so which of them is
+            # "the dominant kernel" (the longest; `kernel`, `frac` above) changes from run to run -- their fractions are all in kernel_frac
+            "dominant_within_5pct": [k for k in flops if kernel_ms_serial[names.index(k)] >= 0.95 * kernel_ms_serial[names.index(roof_kernel)]],
+            "kernel_frac": {k: (tf(flops[k], kernel_ms_serial[names.index(k)]) or 0.0) / FP64_MFMA_PEAK_TFLOPS for k in flops},
+            # the path: FLOPs of one step over the step's share of the timed region (with the overlap on, the launches of one cycle span more than that)
+            "path_achieved": tf(path_flops, ms_per_step) if not emulate else None,
+            "path_frac": (tf(path_flops, ms_per_step) or 0.0) / FP64_MFMA_PEAK_TFLOPS if not emulate else 0.0}
+
+
+def dump_outputs(path, arrays, limit=64 << 20, seed=0):
+    """--dump-outputs: one DIR/<name>.npy per array (float64), all of them indexed by instance on axis 0.  Above `limit` bytes in all (the files' headers
+    included), the same fixed, seeded sample of instances is taken from every array and its indices are written to DIR/instances.npy."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    per_instance = sum(a[0].nbytes for a in arrays.values())
+    budget = limit - 4096 * (len(arrays) + 1)
+    if per_instance * n > budget:
+        keep = np.sort(np.random.default_rng(seed).choice(n, budget // (per_instance + 8), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["instances"] = keep.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def self_launch(args, argv):
     """`python bench.py --gpus N` without a launcher: start N ranks of this script on this node (one per GPU, RCCL over xGMI)."""
     import socket
@@ -362,8 +431,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=120, help="timed steps; the default makes the timed region >= 0.2 s at 1.9 ms per step")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-steady-state", action="store_true", help="skip config.steady_state (the receding-horizon leg, N = 1 only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: result checks, roofline (with its one-stream calibration pass), config.steady_state, "
+                         "cpu_baseline, and config.batch_sweep with --sweep.  Off: set up, warm up, time the steps, dump the outputs, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float64; a fixed, seeded sample of the instances if they exceed 64 MB)")
+    ap.add_argument("--no-steady-state", action="store_true", help="with --full: skip config.steady_state (the receding-horizon leg, N = 1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--no-overlap", action="store_true", help="qmgpu_set_overlap off: every kernel of a step on one stream, one after the other (the kernel times then add up to the step)")
     ap.add_argument("--wbc-state", choices=["carry", "cold"], default="cold", help="steady-state leg: every WBC tick cold as the reference's qpOASES call (default), or the WBC's solver state travels from step to step (qmgpu_wbc_args::working_set)")
     ap.add_argument("--force-collective", action="store_true",
@@ -373,7 +447,7 @@ def main():
     ap.add_argument("--batch-per-gpu", type=int, default=BATCH_PER_GPU, help="only with --emulate / --sweep")
     ap.add_argument("--nodes", type=int, default=HORIZON_N, help="only with --emulate")
     ap.add_argument("--global-batch", type=int, default=CONFIG3_GLOBAL_BATCH, help="only with --emulate: size of the ONE global batch of configs[2] (2048), so that a toy run reaches the 'all of it' branch")
-    ap.add_argument("--sweep", action="store_true", help="N = 1 only: also time 512 / 1024 / 2048 instances on the one GPU (config.batch_sweep)")
+    ap.add_argument("--sweep", action="store_true", help="with --full, N = 1 only: also time 512 / 1024 / 2048 instances on the one GPU (config.batch_sweep)")
     args = ap.parse_args()
     global OVERLAP
     OVERLAP = not args.no_overlap
@@ -510,6 +584,7 @@ def main():
     for _ in range(args.warmup):
         step()
     drain()
+    # the timed steps record their per-kernel HIP events with or without --full (only --full reads them): the headline is measured the same way in both
     sol.enable_timing(True)
     if collective:
         dist.barrier()
@@ -529,78 +604,64 @@ def main():
         dist.all_gather(tall, torch.tensor([elapsed_rank], dtype=torch.float64, device=G.DEVICE))
         elapsed = max(float(t.item()) for t in tall)
         rank_values = [B * args.steps / float(t.item()) for t in tall]
-    kernel_ms = sol.kernel_ms_mean(args.steps)  # [ad, lq, riccati, linesearch, wbc, whole]
+    kernel_ms = sol.kernel_ms_mean(args.steps) if args.full else None  # [ad, lq, riccati, linesearch, wbc, whole]
     sol.enable_timing(False)
 
-    res = mbs[state.get("last", 0)].results(); wres = wbs[state.get("last", 0)].results()
-    # Per-kernel launch durations with the device to themselves (roofline): with the overlap on, ad_node of step k + 1 is LAUNCHED while the WBC of step k still holds the CUs
-    # and its HIP-event interval includes that wait (0.71 instead of 0.37 ms) -- not a property of the kernel.  A short calibration pass of the same cycle on one stream, after
-    # the timed region and outside `value`, gives the unobstructed durations; the kernels the overlap does not touch (lq_node, riccati, line search) measure the same in both.
-    kernel_ms_serial = kernel_ms
-    calibration_same = None
-    if OVERLAP and not args.emulate:
-        cal = max(5, min(args.steps, 20))
-        sol.set_overlap(False); sol.enable_timing(True)
-        for _ in range(cal):
-            sol.cycle(mbs[0].args, t_eval, wbs[0].args)
-        sync()
-        kernel_ms_serial = sol.kernel_ms_mean(cal)
-        sol.enable_timing(False); sol.set_overlap(True)
-        # the calibration pass solves the same cycle as the timed steps (same inputs; inputLast_ has been the cycle's own input since the second step): same results, bit for bit
-        rc, wc = mbs[0].results(), wbs[0].results()
-        calibration_same = bool(np.array_equal(rc["X"], res["X"]) and np.array_equal(rc["U"], res["U"]) and np.array_equal(wc["out"], wres["out"]))
-    ok = bool(np.isfinite(res["X"]).all() and np.isfinite(wres["out"]).all() and (res["stats"][:, 7] == 0).all() and (wres["status"] == 0).all())
-    gather_ok = None
-    if collective:   # this rank's block of the gathered tensor is what it solved, bit for bit; every other block is finite and carries that rank's initial states
-        full = gathered.cpu().numpy()
-        gX, gU, gW, gM = sharding.unpack(full[rank * B:(rank + 1) * B], N)
-        gather_ok = bool(np.array_equal(gX, res["X"]) and np.array_equal(gU, res["U"]) and np.array_equal(gW, wres["out"]) and np.array_equal(gM, res["mode"].astype(np.float64)))
-        if world > 1:
-            aX, _, aW, _ = sharding.unpack(full, N)
-            gather_ok = gather_ok and bool(np.isfinite(full).all() and np.array_equal(aX[:, 0], glob["x0"][:world * B]))
+    if args.dump_outputs and rank == 0:
+        if collective:   # what a caller of the multi-rank path receives: the gathered trajectories, torques and modes of every rank
+            gX, gU, gW, gM = sharding.unpack(gathered.cpu().numpy(), N)
+            dump_outputs(args.dump_outputs, dict(X=gX, U=gU, wbc_out=gW, mode=gM))
+        else:
+            r_, w_ = mbs[state.get("last", 0)].results(), wbs[state.get("last", 0)].results()
+            dump_outputs(args.dump_outputs, dict(T=r_["T"], X=r_["X"], U=r_["U"], mode=r_["mode"], stats=r_["stats"],
+                                                 wbc_out=w_["out"], wbc_status=w_["status"], wbc_input_last=w_["input_last"]))
 
-    batch_sweep = None
-    if args.sweep and world == 1 and rank == 0:
-        batch_sweep = {}
-        for b in (512, 1024, 2048):
-            scb = build_scenario(itf, b, seed=0)
-            s2, m2, w2, te2 = make(scb, b)
-            for _ in range(2):
-                s2.cycle(m2.args, te2, w2.args)
-            s2.enable_timing(True)
-            sync(); t1 = time.perf_counter()
-            for _ in range(5):
-                s2.cycle(m2.args, te2, w2.args)
-            sync(); dt_ = time.perf_counter() - t1
-            kms = s2.kernel_ms_mean(5)
-            batch_sweep[str(b)] = {"cycles_per_s": b * 5 / dt_, "ms_per_step": 1e3 * dt_ / 5, "kernel_ms": dict(zip(["ad", "lq", "riccati", "linesearch", "wbc", "whole"], kms))}
-            s2.close()
+    if args.full:
+        res = mbs[state.get("last", 0)].results(); wres = wbs[state.get("last", 0)].results()
+        # Per-kernel launch durations with the device to themselves (roofline): with the overlap on, ad_node of step k + 1 is LAUNCHED while the WBC of step k still holds the CUs
+        # and its HIP-event interval includes that wait (0.71 instead of 0.37 ms) -- not a property of the kernel.  A short calibration pass of the same cycle on one stream, after
+        # the timed region and outside `value`, gives the unobstructed durations; the kernels the overlap does not touch (lq_node, riccati, line search) measure the same in both.
+        kernel_ms_serial = kernel_ms
+        calibration_same = None
+        if OVERLAP and not args.emulate:
+            cal = max(5, min(args.steps, 20))
+            sol.set_overlap(False); sol.enable_timing(True)
+            for _ in range(cal):
+                sol.cycle(mbs[0].args, t_eval, wbs[0].args)
+            sync()
+            kernel_ms_serial = sol.kernel_ms_mean(cal)
+            sol.enable_timing(False); sol.set_overlap(True)
+            # the calibration pass solves the same cycle as the timed steps (same inputs; inputLast_ has been the cycle's own input since the second step): same results, bit for bit
+            rc, wc = mbs[0].results(), wbs[0].results()
+            calibration_same = bool(np.array_equal(rc["X"], res["X"]) and np.array_equal(rc["U"], res["U"]) and np.array_equal(wc["out"], wres["out"]))
+        ok = bool(np.isfinite(res["X"]).all() and np.isfinite(wres["out"]).all() and (res["stats"][:, 7] == 0).all() and (wres["status"] == 0).all())
+        gather_ok = None
+        if collective:   # this rank's block of the gathered tensor is what it solved, bit for bit; every other block is finite and carries that rank's initial states
+            full = gathered.cpu().numpy()
+            gX, gU, gW, gM = sharding.unpack(full[rank * B:(rank + 1) * B], N)
+            gather_ok = bool(np.array_equal(gX, res["X"]) and np.array_equal(gU, res["U"]) and np.array_equal(gW, wres["out"]) and np.array_equal(gM, res["mode"].astype(np.float64)))
+            if world > 1:
+                aX, _, aW, _ = sharding.unpack(full, N)
+                gather_ok = gather_ok and bool(np.isfinite(full).all() and np.array_equal(aX[:, 0], glob["x0"][:world * B]))
+
+        batch_sweep = None
+        if args.sweep and world == 1 and rank == 0:
+            batch_sweep = {}
+            for b in (512, 1024, 2048):
+                scb = build_scenario(itf, b, seed=0)
+                s2, m2, w2, te2 = make(scb, b)
+                for _ in range(2):
+                    s2.cycle(m2.args, te2, w2.args)
+                s2.enable_timing(True)
+                sync(); t1 = time.perf_counter()
+                for _ in range(5):
+                    s2.cycle(m2.args, te2, w2.args)
+                sync(); dt_ = time.perf_counter() - t1
+                kms = s2.kernel_ms_mean(5)
+                batch_sweep[str(b)] = {"cycles_per_s": b * 5 / dt_, "ms_per_step": 1e3 * dt_ / 5, "kernel_ms": dict(zip(["ad", "lq", "riccati", "linesearch", "wbc", "whole"], kms))}
+                s2.close()
 
     if rank == 0:
-        names = ["ad_node_kernel", "lq_node_kernel", "riccati_kernel", "linesearch_kernel", "wbc_kernel"]
-        modes = res["mode"][:, :N]
-        nst = np.array([[bin(int(m)).count("1") for m in row] for row in modes])
-        nc = 3 * nst + 4 * (4 - nst)
-        flops = {k: 0.0 for k in ("ad_node_kernel", "lq_node_kernel", "riccati_kernel")}
-        for v in np.unique(nc):
-            cnt = int((nc == v).sum())
-            for k, f in node_flops(int(v)).items():
-                flops[k] += cnt * f
-        dom_name = max(flops, key=lambda k: kernel_ms_serial[names.index(k)])   # longest launch (device to itself) among the kernels that carry algorithmic FLOPs
-        path_flops = flops["ad_node_kernel"] + flops["lq_node_kernel"] + flops["riccati_kernel"]
-        roof_kernel = dom_name
-        tf = lambda fl, ms: (fl / (ms * 1e-3) / 1e12) if ms > 0 else None   # noqa: E731  (the emulation has no clocks)
-        # ONE source for the roofline block: the kernel, its duration, achieved / frac, kernel_frac and hbm_gbps all come from the one-stream durations (the calibration pass
-        # when the overlap is on, the timed region itself otherwise); the timed region's own interval of the same kernel is reported next to it
-        achieved = tf(flops[roof_kernel], kernel_ms_serial[names.index(roof_kernel)])
-        achieved_timed = tf(flops[roof_kernel], kernel_ms[names.index(roof_kernel)])
-        tag, ctr = profile_counters()
-        traffic = ctr.get(roof_kernel, {}).get("bytes")
-        src = (f"profiles/{tag}_counters.json (separate rocprofv3 --pmc passes of `bench.py --no-cpu-baseline --no-overlap --steps 5`, summarised by tools/make_profile_summaries.py; "
-               "NOT measured in this run)") if tag else "no committed counter set"
-        # HBM GB/s and matrix-core busy per kernel: counter values per launch (committed profile) over THIS run's HIP-event launch times
-        hbm = {k: (ctr[k]["bytes"] / (kernel_ms_serial[names.index(k)] * 1e-3) / 1e9) for k in names if k in ctr and kernel_ms_serial[names.index(k)] > 0}
-        busy = {k: ctr[k]["mfma_busy"] for k in names if k in ctr and "mfma_busy" in ctr[k]}
         out = {
             "metric": "MPC+WBC cycles/sec (AlienGo+Z1, N=100)",
             "value": world * B * args.steps / elapsed,
@@ -620,48 +681,28 @@ def main():
                                    "the timed region ends with a device-wide synchronisation; kernel_ms are per-launch HIP-event durations and now overlap (their sum exceeds ms_per_step); --no-overlap: one stream"
                                    + ("; the all-gather of step k is enqueued behind the launch of step k + 1, from alternating output buffers" if collective else "")) if OVERLAP else "off (--no-overlap): one stream, kernels back to back",
                        "wbc_inputs": "headline: robots at rest, t = 20 s, FIRST tick (inputLast_ = 0: the reference's spurious first-tick joint accelerations, torque limits active); the moving-robot, carried-inputLast_ regime is config.steady_state",
-                       "batch_per_gpu": B, "global_batch": world * B, "horizon_nodes": N, "gait": "trot", "seed": 0 if world == 1 else 1, "results_finite_and_converged": ok,
+                       "batch_per_gpu": B, "global_batch": world * B, "horizon_nodes": N, "gait": "trot", "seed": 0 if world == 1 else 1,
                        "collective": ("all_gather(X,U,tau,mode) over " + ("gloo (emulation)" if args.emulate else "RCCL")) if collective else "none",
                        "per_rank_value": rank_values, "per_rank_value_min": min(rank_values), "per_rank_value_max": max(rank_values),
                        "slowest_rank_over_fastest": min(rank_values) / max(rank_values),
-                       "gathered_bytes_per_step": int(world * B * sharding.pack_len(N) * 8) if collective else 0,
-                       "gather_matches_local_results": gather_ok},
-            "roofline": {"bound": "mfma", "kernel": roof_kernel, "achieved": achieved, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": (achieved / FP64_MFMA_PEAK_TFLOPS) if achieved is not None else None,
-                         "achieved_from_the_timed_regions_interval": achieved_timed, "calibration_pass_reproduces_the_timed_results": calibration_same,
-                         "traffic": traffic, "traffic_source": src,
-                         "mfma_busy": busy.get(roof_kernel), "hbm_gbps": hbm.get(roof_kernel),
-                         "mfma_busy_by_kernel": busy, "hbm_gbps_by_kernel": hbm,
-                         "hbm_bytes_per_step": sum(v["bytes"] for k, v in ctr.items() if isinstance(v, dict) and "bytes" in v) or None,
-                         "counters_note": "mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (launch duration x 2.4 GHz x 1024 SIMDs) of the committed PMC pass; hbm_gbps = committed "
-                                          "(2 x FETCH_SIZE + WRITE_SIZE) bytes per launch / this run's HIP-event launch time; HBM peak 8000 GB/s spec, 6290 GB/s measured copy rate",
-                         "note": "algorithmic dense-contraction FLOPs of SURVEY.md 8(d) per launch / HIP-event kernel time; fp64 matrix peak is the public spec; "
-                                 "the path is latency bound, not MFMA bound (DESIGN.md)",
-                         "kernel_ms": dict(zip(names + ["whole_call"], kernel_ms)),
-                         "kernel_ms_one_stream": dict(zip(names + ["whole_call"], kernel_ms_serial)),
-                         "kernel_ms_note": "kernel_ms: HIP events over the TIMED region (with the overlap on, ad_node's interval includes its wait for the CUs the previous step's WBC still holds, and whole_call spans two "
-                                           "streams); kernel_ms_one_stream: the same cycle on one stream in a calibration pass after the timed region (outside `value`): what `kernel`, kernel_frac and hbm_gbps are computed "
-                                           "from, `achieved` / `frac` included (achieved_from_the_timed_regions_interval: the same FLOPs over the timed region's own interval of that kernel)",
-                         # launches within 5 % of the longest one: since round 3 the three FLOP-carrying kernels take 0.45-0.47 ms each, so which of them is
-                         # "the dominant kernel" (the longest; `kernel`, `frac` above) changes from run to run -- their fractions are all in kernel_frac
-                         "dominant_within_5pct": [k for k in flops if kernel_ms_serial[names.index(k)] >= 0.95 * kernel_ms_serial[names.index(roof_kernel)]],
-                         "kernel_frac": {k: (tf(flops[k], kernel_ms_serial[names.index(k)]) or 0.0) / FP64_MFMA_PEAK_TFLOPS for k in flops},
-                         # the path: FLOPs of one step over the step's share of the timed region (with the overlap on, the launches of one cycle span more than that)
-                         "path_achieved": tf(path_flops, 1e3 * elapsed / args.steps) if not args.emulate else None,
-                         "path_frac": (tf(path_flops, 1e3 * elapsed / args.steps) or 0.0) / FP64_MFMA_PEAK_TFLOPS if not args.emulate else 0.0},
+                       "gathered_bytes_per_step": int(world * B * sharding.pack_len(N) * 8) if collective else 0},
         }
-        if batch_sweep is not None:
-            out["config"]["batch_sweep"] = batch_sweep
-        if world == 1 and not args.no_steady_state and not args.emulate:
-            from qm_door_amd import api as _api
-            sc_ss = dict(sc)
-            # one trot schedule covers the whole leg (QMGPU_MAX_EVENTS = 40 mode switches: ~14 s of trot); a longer --steps is cut to 1000 receding-horizon steps here
-            ss_steps, ss_warm = min(args.steps, 1000), min(args.warmup, 50)
-            t_end = (ss_steps + ss_warm) * 0.01 + N * itf.problem.settings.dt + 0.5
-            sc_ss["nev"], sc_ss["ev"], sc_ss["md"] = _api.GaitSchedule(lib=itf.lib).mode_schedule("trot", 0.0, 0.0, t_end)
-            out["config"]["steady_state"] = steady_state(itf, sc_ss, ss_steps, ss_warm, wbc_state=args.wbc_state)
-        if world == 1 and not args.no_cpu_baseline and not args.emulate:
-            out["cpu_baseline"] = cpu_baseline(itf, sc)
+        if args.full:
+            out["config"]["results_finite_and_converged"] = ok
+            out["config"]["gather_matches_local_results"] = gather_ok
+            out["roofline"] = roofline(res, kernel_ms, kernel_ms_serial, calibration_same, 1e3 * elapsed / args.steps, N, args.emulate)
+            if batch_sweep is not None:
+                out["config"]["batch_sweep"] = batch_sweep
+            if world == 1 and not args.no_steady_state and not args.emulate:
+                from qm_door_amd import api as _api
+                sc_ss = dict(sc)
+                # one trot schedule covers the whole leg (QMGPU_MAX_EVENTS = 40 mode switches: ~14 s of trot); a longer --steps is cut to 1000 receding-horizon steps here
+                ss_steps, ss_warm = min(args.steps, 1000), min(args.warmup, 50)
+                t_end = (ss_steps + ss_warm) * 0.01 + N * itf.problem.settings.dt + 0.5
+                sc_ss["nev"], sc_ss["ev"], sc_ss["md"] = _api.GaitSchedule(lib=itf.lib).mode_schedule("trot", 0.0, 0.0, t_end)
+                out["config"]["steady_state"] = steady_state(itf, sc_ss, ss_steps, ss_warm, wbc_state=args.wbc_state)
+            if world == 1 and not args.no_cpu_baseline and not args.emulate:
+                out["cpu_baseline"] = cpu_baseline(itf, sc)
         print(json.dumps(out), flush=True)
     if collective:
         dist.destroy_process_group()

@@ -13,8 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_line_and_forced_collective():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--force-collective"], capture_output=True,
-                       text=True, timeout=600, env=env, cwd=ROOT)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--force-collective"],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
@@ -57,12 +57,14 @@ def test_bench_scenario_every_instance_against_oracle(interface):
     S.assert_parity(S.parity_report("bench_scenario_configs1_256xN100", got, ref))
 
 
-def test_bench_two_ranks_on_the_emulation_path():
+def test_bench_two_ranks_on_the_emulation_path(tmp_path):
     """CPU: `python bench.py --gpus 2` without a launcher environment starts its own two ranks (torch.distributed.run on 127.0.0.1); with --emulate
-    the kernels are the host-emulated ones and the collective runs over gloo.  End to end: configs[2] shards of ONE global batch, all-gather, the line."""
+    the kernels are the host-emulated ones and the collective runs over gloo.  End to end: configs[2] shards of ONE global batch, all-gather, the line,
+    and rank 0's dump of what the gather delivered (every rank's instances)."""
+    import numpy as np
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--emulate", "--batch-per-gpu", "2", "--nodes", "4", "--steps", "1", "--warmup", "0"],
-                       capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--emulate", "--batch-per-gpu", "2", "--nodes", "4", "--steps", "1", "--warmup", "0",
+                        "--full", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1                       # rank 0 prints the one line
@@ -73,6 +75,9 @@ def test_bench_two_ranks_on_the_emulation_path():
     assert cfg["gather_matches_local_results"] is True and cfg["results_finite_and_converged"] is True
     assert len(cfg["per_rank_value"]) == 2 and cfg["collective"].startswith("all_gather")
     assert "EMULATED" in d["data"] and "cpu_baseline" not in d
+    X, mode = np.load(tmp_path / "X.npy"), np.load(tmp_path / "mode.npy")
+    assert X.dtype == np.float64 and X.shape == (4, 5, 30) and mode.shape == (4, 5) and np.isfinite(X).all()
+    assert sorted(f.name for f in tmp_path.iterdir()) == ["U.npy", "X.npy", "mode.npy", "wbc_out.npy"]
 
 
 def test_bench_eight_ranks_take_the_whole_global_batch_on_the_emulation_path():
@@ -80,7 +85,7 @@ def test_bench_eight_ranks_take_the_whole_global_batch_on_the_emulation_path():
     shards, all-gather, the line -- at toy size on the host-emulated kernels over gloo (--global-batch 8: one instance per rank)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--emulate", "--batch-per-gpu", "1", "--global-batch", "8", "--nodes", "4", "--steps", "1",
-                        "--warmup", "0"], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
+                        "--warmup", "0", "--full"], capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -89,6 +94,76 @@ def test_bench_eight_ranks_take_the_whole_global_batch_on_the_emulation_path():
     assert d["n_gpus"] == 8 and cfg["global_batch"] == 8 and cfg["batch_per_gpu"] == 1 and len(cfg["per_rank_value"]) == 8
     assert cfg["workload"].startswith("configs[2]: ONE global batch of 8 MPC instances (all of the 8 of seed 1)")
     assert cfg["gather_matches_local_results"] is True and cfg["results_finite_and_converged"] is True
+
+
+HEADLINE = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup")
+FULL_ONLY = ("roofline", "cpu_baseline")
+FULL_ONLY_CONFIG = ("results_finite_and_converged", "gather_matches_local_results", "steady_state", "batch_sweep")
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """CPU (host-emulated kernels, one rank): without --full the line is the headline and nothing else, --steps is the number of timed steps, and
+    --dump-outputs writes the last step's results as float64 .npy files -- the same numbers in two runs with the same arguments, and in a --full run."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--emulate", "--batch-per-gpu", "2", "--nodes", "4", "--steps", "2", "--warmup", "1"]
+    dumps = []
+    for i, extra in enumerate(([], [], ["--full"])):
+        d_out = tmp_path / str(i)
+        p = subprocess.run(cmd + extra + ["--dump-outputs", str(d_out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert all(k in d for k in HEADLINE) and d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+        assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) < 1e-9 * d["value"]          # B instances per step over the step's milliseconds
+        if extra:
+            assert "roofline" in d and d["config"]["results_finite_and_converged"] is True
+        else:
+            assert not [k for k in FULL_ONLY if k in d] and not [k for k in FULL_ONLY_CONFIG if k in d["config"]]
+        dumps.append({f.name: np.load(f) for f in d_out.iterdir()})
+    assert sorted(dumps[0]) == ["T.npy", "U.npy", "X.npy", "mode.npy", "stats.npy", "wbc_input_last.npy", "wbc_out.npy", "wbc_status.npy"]
+    assert dumps[0]["X.npy"].shape == (2, 5, 30) and dumps[0]["wbc_out.npy"].shape == (2, 54)
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float64 and np.isfinite(a).all(), name
+        assert np.array_equal(a, dumps[1][name]) and np.array_equal(a, dumps[2][name]), name
+
+
+def test_dump_outputs_keeps_a_fixed_seeded_sample_under_the_limit(tmp_path):
+    """bench.dump_outputs: above the size limit the same seeded subset of instances is taken from every array, its indices are stored next to them,
+    and the files stay within the limit; below it everything is written as it is."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = dict(X=rng.standard_normal((1000, 11, 30)), mode=rng.integers(0, 15, (1000, 11)).astype(np.int32))
+    limit = 1 << 20
+    for d_out in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d_out), arrays, limit=limit)
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == ["X.npy", "instances.npy", "mode.npy"]
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= limit
+    idx = np.load(tmp_path / "a" / "instances.npy").astype(np.int64)
+    assert 0 < len(idx) < 1000 and (np.diff(idx) > 0).all()
+    X, mode = np.load(tmp_path / "a" / "X.npy"), np.load(tmp_path / "a" / "mode.npy")
+    assert X.dtype == mode.dtype == np.float64 and np.array_equal(X, arrays["X"][idx]) and np.array_equal(mode, arrays["mode"][idx])
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))
+    bench.dump_outputs(str(tmp_path / "c"), arrays)
+    assert sorted(f.name for f in (tmp_path / "c").iterdir()) == ["X.npy", "mode.npy"] and np.array_equal(np.load(tmp_path / "c" / "X.npy"), arrays["X"])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_on_the_gpu(tmp_path):
+    """The command every change is measured with, on the GPU: the headline only, and the dump of the last timed step (256 instances, N = 100)."""
+    import numpy as np
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert all(k in d for k in HEADLINE) and d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert not [k for k in FULL_ONLY if k in d] and not [k for k in FULL_ONLY_CONFIG if k in d["config"]]
+    X, out, status = np.load(tmp_path / "X.npy"), np.load(tmp_path / "wbc_out.npy"), np.load(tmp_path / "wbc_status.npy")
+    assert X.shape == (256, 101, 30) and out.shape == (256, 54) and np.isfinite(X).all() and np.isfinite(out).all() and (status == 0).all()
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64 << 20
 
 
 def test_bench_refuses_a_changed_workload_outside_the_emulation():

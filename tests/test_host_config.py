@@ -165,27 +165,21 @@ def test_bench_cpu_baseline_leg_runs(interface):
     assert out["one_thread"] > 0 and out["three_threads_over_nodes"] > 0 and abs(sum(out["one_thread_split_percent"].values()) - 100.0) < 0.1
 
 
-REFERENCE = "/root/reference"
+# the maintainer's original task.info / reference.info (qm_controllers/config/) and the URDF they load (qm_description/urdf/quadruped_manipulator/robot.urdf),
+# stored unchanged as test fixtures
+REFERENCE_CONFIG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_config")
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "qm_controllers", "config")), reason="the reference tree is not mounted (GPU boxes)")
 def test_loader_reads_the_reference_own_files_into_the_same_problem(hip_lib):
     """the oracle receives its problem through the product's loader, and the product ships values DISTILLED from the reference's files
-    (tools/distill_reference_config.py).  Where the reference tree is mounted, qmgpu_load_problem on the maintainer's ORIGINAL task.info / robot.urdf /
-    reference.info (gains NULL: the task file carries them) must produce, byte for byte, the qmgpu_problem it produces from qm_door_amd/data/."""
-    import glob
-    cfg = os.path.join(REFERENCE, "qm_controllers", "config")
-    task, ref = os.path.join(cfg, "task.info"), os.path.join(cfg, "reference.info")
-    urdfs = [p for p in glob.glob(os.path.join(REFERENCE, "**", "*.urdf"), recursive=True) if "robot" in os.path.basename(p) or "aliengo" in os.path.basename(p).lower()]
-    assert os.path.exists(task) and os.path.exists(ref) and urdfs, (task, ref, urdfs)
+    (tools/distill_reference_config.py).  qmgpu_load_problem on the maintainer's ORIGINAL task.info / robot.urdf / reference.info (tests/golden/reference_config/;
+    gains NULL: the task file carries them) must produce, byte for byte, the qmgpu_problem it produces from qm_door_amd/data/."""
+    task, ref = os.path.join(REFERENCE_CONFIG, "task.info"), os.path.join(REFERENCE_CONFIG, "reference.info")
+    urdf = os.path.join(REFERENCE_CONFIG, "robot.urdf")
+    assert os.path.exists(task) and os.path.exists(ref) and os.path.exists(urdf), (task, ref, urdf)
     d = abi.DATA_DIR.encode()
     ours = abi.Problem()
     assert hip_lib.qmgpu_load_problem(d + b"/task.info", d + b"/aliengo_z1.urdf", d + b"/reference.info", None, C.byref(ours)) == 0, hip_lib.qmgpu_last_error()
-    matched = []
-    for urdf in urdfs:
-        theirs = abi.Problem()
-        if hip_lib.qmgpu_load_problem(task.encode(), urdf.encode(), ref.encode(), None, C.byref(theirs)) != 0:
-            continue
-        if bytes(theirs) == bytes(ours):
-            matched.append(urdf)
-    assert matched, ("no URDF of the reference tree reproduces the shipped problem", urdfs)
+    theirs = abi.Problem()
+    assert hip_lib.qmgpu_load_problem(task.encode(), urdf.encode(), ref.encode(), None, C.byref(theirs)) == 0, hip_lib.qmgpu_last_error()
+    assert bytes(theirs) == bytes(ours), "the reference's own files do not reproduce the shipped problem"

@@ -3,7 +3,7 @@
 import sqlite3, sys
 c = sqlite3.connect(sys.argv[1])
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 40
-off = int(sys.argv[3]) if len(sys.argv) > 3 else 0      # skip that many kernels at the end (bench.py ends with a one-stream calibration pass of 20 cycles)
+off = int(sys.argv[3]) if len(sys.argv) > 3 else 0      # skip that many kernels at the end (bench.py --full ends with a one-stream calibration pass of 20 cycles)
 rows = c.execute("select name, start, start + duration, queue_id from kernels order by start").fetchall() if True else []
 rows = rows[-(n + off):len(rows) - off]
 t0 = rows[0][1]

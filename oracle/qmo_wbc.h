@@ -329,15 +329,11 @@ constexpr double kAsLamTol = 8.0;            // a multiplier counts once it exce
 constexpr int kAsMaxWorkingSetChanges = 100; // nWSR of HoQp.cpp:141
 constexpr int kHeldFormMaxIterations = 4;    // the held-variable form of a level with own rows (solveLevel) is given up beyond this many iterations: status 6, the interior point takes over (= QP_HELD_CAP of the kernels)
 constexpr int kAsMaxPinned = 28;             // = QP_KMAX of the kernels (qp_dev.h): rows the small system of the pinned set holds
+constexpr int kLiteralRegMaxN = 12;          // levels of at most this many variables keep HoQp's 1e-12 I IN the factorised matrix and the gradient (LevelQp::lit)
 // Experiment knobs (qmo_set_experiment; defaults = the product's algorithm).  inline: one copy whatever the number of translation units; written between batches only.
 inline double g_expLowerLevelStart = kLowerLevelStart;   // another starting value of the interior point = another path to the same vertex (tests: the result must not depend on it)
-inline int g_expNoMinNormStart = 0;                      // 1: the first level without its minimum-norm start (tests: same torques)
 inline int g_expNoInteriorPoint = 0;                     // 1: the active-set method alone, cold from z = 0 on every level (tests: same vertex)
-inline int g_expGuessOrder = 1;
-inline int g_expLiteralRegMaxN = 12;                     // levels of at most this many variables keep HoQp's 1e-12 I IN the factorised matrix and the gradient (LevelQp::lit); 0: the limit everywhere, as until round 5
-inline int g_expCanonicalFirst = 1;                      // HierarchicalMpcWbc takes the canonical representative at every level from the first pass on (0: only when directions are left over at the end, as until round 6)
-inline int g_expOwnInteriorPoint = 3;                    // a level with own rows whose held-variable form is rejected (torque limits that cannot hold) runs the interior point, own rows as penalised slacks, in front of its active-set method (0: cold from z = 0, as until round 6: 40-46 changes on diverged robots)
-inline double g_expIpmStartDelta = 0.0;                  // experiment, off: inherited rows of the interior point started on their margins (interiorPointPhase has what it did)
+inline bool g_expOwnInteriorPoint = true;                // a level with own rows whose held-variable form is rejected (torque limits that cannot hold) runs the interior point, own rows as penalised slacks, in front of its active-set method (false: cold from z = 0, as until round 6: 40-46 changes on diverged robots)
 inline int g_expNoWarmStart = 0;                         // 1: the working set carried from the previous tick (wbcUpdate: ws) is ignored -- every level cold (tests: same torques)
 inline int g_expTrace = 0;                               // per-iteration trace on stderr
 
@@ -451,15 +447,12 @@ inline int interiorPointPhase(const LevelQp& q, const LevelWork& w, double sigma
   const double scale = w.scale, sigma = sigma0 * std::sqrt(w.scale);
   Vec z(n, 0.0), s(mr), lam(mr, sigma);
   std::vector<char> soft(mr, 0); for (int r = 0; r < mr; ++r) soft[r] = rows[r] < q.mOwn;
-  if (g_expIpmStartDelta > 0.0 && !ownRows) {
-    // Experiment of round 6, measured and NOT kept (default 0 = off): inherited rows started ON their margins and centred, s = max(f, delta |d|_inf), lam = sigma^2 / s, instead of
-    // s = lam = sigma (1.5e3 next to margins of 0-90: a start 1.4e3 outside every row, from which the diverged robots of the bench's steady-state leg crawl for ten iterations
-    // at step lengths of 1-5 %).  delta = 10: second-level iterations on those robots 13.5 -> 9.3 in the mean, 23 -> 13 at most, regular closed-loop ticks 5.4 -> 5.2, their
-    // ticks on the GPU 0.82 -> 0.66 ms -- but another path to the vertex: ONE tick of the static walk's 76,800 (HierarchicalWbc, where every tick had been within 1e-6) came out
-    // 6e-3 apart between GPU and this restatement, on a tick whose torques move by 5e-3 under 1e-9 input noise on this side alone, and one instance of the 120-step bench leg
-    // took 47 passes.  Parity on every tick is worth more than 0.15 ms on three robots.
-    for (int i = 0; i < mr; ++i) { s[i] = std::max(f[i], g_expIpmStartDelta * w.dn[rows[i]]); lam[i] = sigma * sigma / s[i]; }
-  } else
+  // (Measured in round 6 and NOT kept: inherited rows started ON their margins and centred, s = max(f, delta |d|_inf), lam = sigma^2 / s, instead of s = lam = sigma
+  //  (1.5e3 next to margins of 0-90: a start 1.4e3 outside every row, from which the diverged robots of the bench's steady-state leg crawl for ten iterations at step lengths
+  //  of 1-5 %).  delta = 10: second-level iterations on those robots 13.5 -> 9.3 in the mean, 23 -> 13 at most, regular closed-loop ticks 5.4 -> 5.2, their ticks on the GPU
+  //  0.82 -> 0.66 ms -- but another path to the vertex: ONE tick of the static walk's 76,800 (HierarchicalWbc, where every tick had been within 1e-6) came out 6e-3 apart
+  //  between GPU and this restatement, on a tick whose torques move by 5e-3 under 1e-9 input noise on this side alone, and one instance of the 120-step bench leg took
+  //  47 passes.  Parity on every tick is worth more than 0.15 ms on three robots.)
   for (int i = 0; i < mr; ++i) {
     if (!soft[i]) s[i] = std::max(sigma, f[i]);
     else if (f[i] >= 0.0) s[i] = f[i] + sigma;             // s - lam = f at z = 0: the row's equation holds from the start
@@ -578,7 +571,7 @@ inline QpStats activeSetPhase(const LevelQp& q, const LevelWork& w, const IpmPoi
       //  the time: released with a negative multiplier one iteration later, the other pinned by a zero-length step after that -- two factorisations for nothing)
       std::vector<int> gs;
       for (int r = 0; r < m; ++r) if (rowOn[r] && state[r] == P && guess[r]) gs.push_back(r);
-      if (start && start->usable && g_expGuessOrder) std::stable_sort(gs.begin(), gs.end(), [&](int a, int b) { return start->lam[a] * w.dn[a] > start->lam[b] * w.dn[b]; });
+      if (start && start->usable) std::stable_sort(gs.begin(), gs.end(), [&](int a, int b) { return start->lam[a] * w.dn[a] > start->lam[b] * w.dn[b]; });
       for (int r : gs) pin.push_back(r);
       // (the kernels' small system holds kAsMaxPinned rows; of a larger guess -- the interior point of a degenerate level: dozens of zero-margin rows with multiplier above
       //  slack -- the rows with the smallest estimates stay out, on both sides; the ratio test meets them again if the step crosses them)
@@ -806,7 +799,7 @@ inline QpStats solveLevel(LevelQp q, std::vector<char>& eq, Vec& z, uint64_t* wa
   //   z = (A Z)' y,   (A Z)(A Z)' y = -rhat        (a Cholesky of the size of the TASK: 18 instead of 36)
   // -- contact forces that carry the robot and small accelerations, inside the friction cones and the torque limits in every regular tick.  Taken if it is: every own
   // row strictly satisfied (then no row is active, the point is the level's minimiser AND its canonical representative: wbcUpdate needs no completion here).
-  if (q.mOwn > 0 && q.mOwn == m && q.AZ.r > 0 && q.AZ.r <= q.n() && !g_expNoMinNormStart) {
+  if (q.mOwn > 0 && q.mOwn == m && q.AZ.r > 0 && q.AZ.r <= q.n()) {
     const int r = q.AZ.r, n = q.n();
     Mat Gd(r, r);
     // (weighted norm: the variables the zero-bound rows act on -- the contact forces under their cones -- are cheap, kMinNormCheap x, so that forces carry the robot and
@@ -841,19 +834,17 @@ inline QpStats solveLevel(LevelQp q, std::vector<char>& eq, Vec& z, uint64_t* wa
     //  of from z = 0: on the eleven slowest ticks of the bench's steady-state leg, robots whose torque limits cannot hold, 58-72 working-set changes instead of 40-46.)
     if (g_expTrace) fprintf(stderr, "  minimum-norm start of the level: %s\n", ok ? "taken" : "rejected");
   }
-  if (!solved && q.mOwn > 0 && q.mOwn == m && g_expOwnInteriorPoint == 2) {
-    ipmIt = interiorPointPhase(q, w, g_expLowerLevelStart, pt, kIpmHandOverMu, false, 0, true);
-  } else if (!solved && q.mOwn > 0) {
+  if (!solved && q.mOwn > 0) {
     std::vector<char> fixedVars(q.n(), 0); bool any = false;
     for (int i = 0; i < q.mOwn; ++i) if (w.on[i] && std::fabs(q.f[i]) <= 1e-9 * w.scale) for (int j = 0; j < q.n(); ++j) if (q.D(i, j) != 0.0) { fixedVars[j] = 1; any = true; }
     if (any) {
-      st = activeSetPhase(q, w, nullptr, zw, lam, state, &fixedVars, nullptr, nullptr, nullptr, g_expOwnInteriorPoint == 3 ? kHeldFormMaxIterations : kAsMaxWorkingSetChanges);
+      st = activeSetPhase(q, w, nullptr, zw, lam, state, &fixedVars, nullptr, nullptr, nullptr, g_expOwnInteriorPoint ? kHeldFormMaxIterations : kAsMaxWorkingSetChanges);
       solved = st.status == 0;
       if (!solved && g_expTrace) fprintf(stderr, "  held-variable form rejected (status %d): the zero-bound rows as rows\n", st.status);
       // (round 6) rejected means the cost wants the held forces moved: limits are violated wherever the task is met.  From z = 0 the active-set method then changes one row per
       // iteration -- 40-46 of them on robots whose plan has diverged, the tail of the bench's steady-state leg --; the interior point moves all rows at once and hands over
       // the side of its bound every row ends on.
-      if (!solved && (g_expOwnInteriorPoint == 1 || g_expOwnInteriorPoint == 3) && q.mOwn == m) ipmIt = interiorPointPhase(q, w, g_expLowerLevelStart, pt, kIpmHandOverMu, false, 0, true);
+      if (!solved && g_expOwnInteriorPoint && q.mOwn == m) ipmIt = interiorPointPhase(q, w, g_expLowerLevelStart, pt, kIpmHandOverMu, false, 0, true);
       if (solved) for (int i = 0; i < q.mOwn; ++i) if (w.on[i] && std::fabs(q.f[i]) <= 1e-9 * w.scale && state[i] == 0) { state[i] = 1; lam[i] = 0.0; }   // (reported as pinned with a vanishing multiplier: what they are)
     }
   }
@@ -937,7 +928,7 @@ struct HoQp {
     Vec sol(nz, 0.0);
     if (numDec > 0) {
       const int mAll = numSlack + numPrevSlack;
-      LevelQp q; q.G0 = zz0; q.g = Vec(cv.begin(), cv.begin() + numDec); if (hasEq) { q.AZ = aZ; q.rhat = task.a * xPrev - task.b; } q.D = Mat(mAll, numDec); q.f = Vec(mAll, 0.0); q.mOwn = numSlack; q.reg = hasEq ? 1e-12 : 0.0; q.lit = hasEq && numSlack == 0 && numDec <= g_expLiteralRegMaxN;
+      LevelQp q; q.G0 = zz0; q.g = Vec(cv.begin(), cv.begin() + numDec); if (hasEq) { q.AZ = aZ; q.rhat = task.a * xPrev - task.b; } q.D = Mat(mAll, numDec); q.f = Vec(mAll, 0.0); q.mOwn = numSlack; q.reg = hasEq ? 1e-12 : 0.0; q.lit = hasEq && numSlack == 0 && numDec <= kLiteralRegMaxN;
       for (int i = 0; i < numSlack; ++i) { for (int j = 0; j < numDec; ++j) q.D(i, j) = Dm(numSlack + numPrevSlack + i, j); q.f[i] = fv[numSlack + numPrevSlack + i]; }
       for (int i = 0; i < numPrevSlack; ++i) { for (int j = 0; j < numDec; ++j) q.D(numSlack + i, j) = Dm(numSlack + i, j); q.f[numSlack + i] = fv[numSlack + i]; }
       std::vector<char> eqr(mAll, 0);
@@ -1022,7 +1013,7 @@ inline int wbcUpdate(const qmgpu_problem& P, int variant, const double* xDes, co
   // back to the point the level above returned, which its own regulariser had made the minimum-norm one.  That controller therefore takes the canonical representative at every
   // level from the first pass on (measured against the 50-digit solution of the reference's QPs, tools/hoqp_exact.py: leg torques median 2.9e-8 -> 1.3e-10, and the answer stops
   // depending on the path to the vertex: 23 of 512 stress instances above 1e-9 -> 1).  HierarchicalWbc's last level sees everything that is left strongly; it keeps the rule above.
-  bool canonical = g_expCanonicalFirst && variant == 1;
+  bool canonical = variant == 1;
   // The working sets of the previous tick (one word per solve: [1 + 6 pass + 2 level + completion]) are guesses for this one as long as the rows mean the same thing:
   // same contact mode, controller and task set (word 0); anything else starts cold.  Words 13 / 14: passes of every solve of this tick (a byte each, bit 7 = guess refuted).
   if (ws) {

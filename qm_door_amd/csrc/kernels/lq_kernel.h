@@ -161,11 +161,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 
   // (the record stores stay ordinary stores: as streaming stores -- QM_STREAM_STORE, which ad_node_kernel uses for its rows -- they made this kernel slower,
   //  0.656 -> 0.686 ms, and streaming loads of the AD rows as well, 0.656 -> 0.676 ms; measured in round 3)
-#ifdef QM_LQ_SAMEREC   // timing experiment only: every node writes the same record (no HBM write traffic)
-  real* rec = a.stages + size_t(blockIdx.x & 255) * STAGE_DOUBLES;
-#else
   real* rec = a.stages + (size_t(inst) * (a.N + 1) + node) * STAGE_DOUBLES;
-#endif
   real* dbg = a.debug ? a.debug + (size_t(inst) * (a.N + 1) + node) * DBG_DOUBLES : nullptr;
   int tIdx; real tAlpha;
   timeSegment(tTimes, a.K, t, tIdx, tAlpha);

@@ -18,10 +18,8 @@
 
 namespace qmk {
 
-#if defined(QM_QP_TRACE) && !defined(QMGPU_HOST_EMULATION)
+#ifdef QM_QP_TRACE
 #define QP_TRACE_ON (blockIdx.x == (QM_QP_TRACE) && lane == 0)      // experiments only: device printf of one instance's active-set iterations
-#else
-#define QP_TRACE_ON (lane == 0)
 #endif
 constexpr double QP_EPS = 2.220446049250313e-16;
 constexpr double QP_REG = 1e-12;             // HoQp's regulariser (HoQp.cpp:66): a direction it alone would carry counts as having no curvature (x10)
@@ -401,7 +399,7 @@ __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, i
       const double nanProbe = allSum(rdz + rp1);  // NaN anywhere -> NaN here (fmax drops NaNs)
       // a late Newton step of a degenerate problem (barrier weights ~1e18) can lose all accuracy: the previous iterate is what the active-set method starts from
       if (ipmIt > itStart && (!(nanProbe == nanProbe) || !(mu == mu) || nrd > 100.0 * fmax(nrdPrev, 1e-9 * scale))) { zc = zcPrev; s1 = s1p; l1 = l1p; usable = true; break; }
-#if defined(QMGPU_EMU_DEBUG) || defined(QM_QP_TRACE)
+#ifdef QM_QP_TRACE
       if (QP_TRACE_ON) printf("EMU   ipm it %d n %d mu/s %.3e nrd/s %.3e nrp/s %.3e\n", ipmIt, n, mu / scale, nrd / scale, nrp / scale);
 #endif
       if (nrd <= 1e-4 * scale && nrp <= 1e-9 * scale && mu <= muTarget * scale) { usable = true; break; }               // the working set can be read: over to the active-set method, for good
@@ -516,11 +514,10 @@ __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, i
       // same lane only (LDS is in order within a wavefront).  Directions without curvature: their row of L is the unit vector, their right-hand side entry zero (exMask).
       QM_WAVE_SYNC();
       if (lane < NP) io.wtL[lane] = myInv;                       // (the row weights of the K tiles are no longer needed)
-      int* rowOfSlot = reinterpret_cast<int*>(ms);               // [QP_KMAX] ints over the small system's right-hand side (rebuilt by every pass)
-      if (pinned) rowOfSlot[slot] = lane;
+      if (pinned) ms[slot] = double(lane);                       // the row of each slot, in the small system's right-hand side (rebuilt by every pass; exact: rows < 64)
       QM_WAVE_SYNC();
       const int sa = lane < k ? lane : 0;
-      const int myRow = rowOfSlot[sa];
+      const int myRow = int(ms[sa]);
       QM_WAVE_SYNC();
       {
         // four rows of L at a time: the part of their dot products that lies left of the block shares the lane's loads of its own t (one load of t feeds four multiply-adds, four
@@ -607,7 +604,7 @@ __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, i
     const bool offBound = qmBallot(pinned && guess) != 0ull;
     const bool depGuess = qmBallot(pinned && guess && ((depMask >> slot) & 1ull)) != 0ull;     // (a dependency among rows already on their bounds is harmless: skipped by the solve)
     if (offBound && depGuess) {     // a guess with dependent rows: those leave first -- the ratio test meets them again if the step crosses them
-#if defined(QMGPU_EMU_DEBUG) || defined(QM_QP_TRACE)
+#ifdef QM_QP_TRACE
       if (QP_TRACE_ON) printf("EMU   AS it %d: dependent rows of the guess leave (k %d dep %llx)\n", it, k, depMask);
 #endif
       if (pinned && guess && ((depMask >> slot) & 1ull)) { state = ST_I; guess = false; }
@@ -707,7 +704,7 @@ __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, i
       QM_WAVE_SYNC();
       const double Dp = rowDot();
       QM_TICK(6);
-#if defined(QMGPU_EMU_DEBUG) || defined(QM_QP_TRACE)
+#ifdef QM_QP_TRACE
       { const double pm_ = allMax(fabs(pC)); if (QP_TRACE_ON) printf("EMU   AS it %d n %d k %d dep %llx ex %llx offBound %d fullSteps %d pmax %.3e\n", it, n, k, depMask, exMask, int(offBound), fullSteps, pm_); }
 #endif
       const double nanProbe = allSum(pC);
@@ -730,7 +727,7 @@ __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, i
       if (amin < 1.0 && offBound && ipmOn && resumed < 2 && changes == 0) { refuted = true; done = true; break; }     // the guess is refuted before anything moved: back to the interior point
       if (amin < 1.0) {
         const int block = qmFirstBit(qmBallot(a == amin));          // ties keep the smallest row index
-#if defined(QMGPU_EMU_DEBUG) || defined(QM_QP_TRACE)
+#ifdef QM_QP_TRACE
         if (QP_TRACE_ON) printf("EMU     blocked by row %d at alpha %.3e\n", block, amin);
 #endif
         const bool moved = amin * pmax > 1e-13 * zmax0;             // a step that does not move the point beyond its rounding counts as zero-length
@@ -760,7 +757,7 @@ __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, i
       const double worst = allMax(bad);
       if (worst > 1.0) {
         const int rel = qmFirstBit(qmBallot(bad == worst));
-#if defined(QMGPU_EMU_DEBUG) || defined(QM_QP_TRACE)
+#ifdef QM_QP_TRACE
         if (QP_TRACE_ON) printf("EMU     release row %d (worst %.3e)\n", rel, worst);
 #endif
         if (lane == rel) { state = (own && lam > 0.0) ? ST_V : ST_I; lam = 0.0; }

@@ -18,9 +18,6 @@
 #include <type_traits>
 #include "../../../include/qmgpu.h"
 #include "gpu_rt.h"
-#ifndef QMGPU_DEBUG_INST
-#define QMGPU_DEBUG_INST 0
-#endif
 #include "linesearch_kernel.h"  // DblIn
 #include "sweep_dev.h"
 #include "qp_dev.h"
@@ -72,30 +69,13 @@ constexpr int WBC_THREADS = 256;   // the solving wavefront + three helpers (one
 constexpr int MI_FOOTPM = 0, MI_FOOTVM = 12, MI_FOOTDJV = 24, MI_FOOTPD = 36, MI_FOOTVD = 48, MI_EEPM = 60, MI_EEVM = 63, MI_EEWM = 66, MI_EEDJL = 69, MI_EEDJA = 72,
               MI_EERM = 75, MI_EEPD = 84, MI_EEVD = 87, MI_EERD = 90, MI_AL0 = 99, MI_BACC = 102, MI_JACC = 108 /*18*/, MI_BAX = 126 /*measured base Euler axes, 9*/;
 
-// -DQM_WBC_DUMP (tools/wbc_variants.py, experiments only): instance 0 copies its whole LDS carve to a device symbol at a few checkpoints, so that two
-// build variants of the kernel can be compared array by array (qmgpu_debug_wbc_dump).  The product build compiles every QM_WBC_CHECKPOINT to nothing.
-#if defined(QM_WBC_DUMP) && !defined(QMGPU_HOST_EMULATION)
-constexpr int WBC_DUMP_POINTS = 8;
-__device__ double qmWbcDump[WBC_DUMP_POINTS * 17000];
-#define QM_WBC_CHECKPOINT(cp) do { if (blockIdx.x == 0 && wave == 0) { QM_WAVE_SYNC(); for (int e_ = lane; e_ < WBC_LDS_DOUBLES; e_ += 64) qmk::qmWbcDump[(cp) * 17000 + e_] = lds[e_]; QM_WAVE_SYNC(); } } while (0)
-#else
-#define QM_WBC_CHECKPOINT(cp)
-#endif
 __device__ __forceinline__ void cross3(const double* a, const double* b, double* o) { o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0]; }
 __device__ __forceinline__ double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
 // Recursive pass: placements, twists and bias accelerations (generalized accelerations: 0 for the base, qddj for joints).
 // The five kinematic chains hanging off the base (four legs of three joints, the arm of six: checked in qmgpu_create) are walked side by
 // side, chain c in lane c; every lane publishes the bodies of its own chain to LDS, lane 0 the base as well.
-#ifndef QM_WBC_EXP
-#define QM_WBC_EXP 0     // experiments of tools/wbc_variants.py on the opaque-base failure; 0 in the product
-#endif
-#if QM_WBC_EXP == 2
-__device__ __forceinline__ void bodyPass(
-#else
-__device__ inline void bodyPass(
-#endif
-const qmgpu_model& md, const double* q, const double* v, const double* qddj, double* body, double* dof, int lane) {
+__device__ inline void bodyPass(const qmgpu_model& md, const double* q, const double* v, const double* qddj, double* body, double* dof, int lane) {
   double sz, cz, sy, cy, sx, cx;
   qmSinCos(q[3], sz, cz); qmSinCos(q[4], sy, cy); qmSinCos(q[5], sx, cx);
   double R0[9] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, -sy, cy * sx, cy * cx};  // row major
@@ -404,16 +384,14 @@ __device__ __attribute__((noinline)) int wbcNullSpace(int rowsOff, int r, int n,
 }
 
 __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(WbcArgs a) {
-#if defined(QM_WBC_OPAQUE_MASK) && !defined(QMGPU_HOST_EMULATION)
-  // Experiment (tools/wbc_variants.py): array group g of the LDS carve is addressed through one opaque
-  // address-space-3 base register when bit g of the mask is set (round 2's "whole base opaque" = mask 31 returned wrong torques).
   QM_DYNAMIC_LDS(lds);
+#if defined(QM_WBC_OPAQUE_LDS) && !defined(QMGPU_HOST_EMULATION)
+  // Build variant (tools/wbc_variants.py): the arrays of the carve are addressed through one opaque address-space-3 base
+  // register (round 2: wrong torques with IPRA on, correct with it off).
   QM_OPAQUE_LDS(double, ldsO, lds);
-  double* ldsQ = (double*)ldsO;
-#define QM_WBC_BASE(g) ((((QM_WBC_OPAQUE_MASK) >> (g)) & 1) ? ldsQ : lds)
+  double* carve = (double*)ldsO;
 #else
-  QM_DYNAMIC_LDS(lds);
-#define QM_WBC_BASE(g) lds
+  double* carve = lds;
 #endif
   QM_POISON_LDS(lds, WBC_LDS_DOUBLES);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, inst = blockIdx.x;
@@ -423,15 +401,14 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
   const qmgpu_settings& st = a.P->settings;
   double fe[3] = {0.0, 0.0, 0.0};   // external force on the arm end-effector (force tracking; zero otherwise)
   if (a.eeForce) for (int i = 0; i < 3; ++i) fe[i] = a.eeForce[size_t(inst) * 3 + i];
-  // opaque-mask groups: 0 inputs | 1 coordinates | 2 model | 3 task equalities | 4 task inequalities | 5 QP matrices | 6 small vectors | 7 row vectors | 8 exchange scratch + control words
-  double* in = QM_WBC_BASE(0) + W_IN; double* rbd = in; double* xDes = in + 55; double* uDes = in + 85; double* il = in + 115;
-  double* qM = QM_WBC_BASE(1) + W_Q; double* vM = qM + 24; double* qD = qM + 48; double* vD = qM + 72;
-  double* body = QM_WBC_BASE(2) + W_BODY; double* dof = QM_WBC_BASE(2) + W_DOF; double* wr = QM_WBC_BASE(2) + W_WR; double* M = QM_WBC_BASE(2) + W_M; double* nle = QM_WBC_BASE(2) + W_NLE;
-  double* Jf = QM_WBC_BASE(2) + W_JF; double* Ja = QM_WBC_BASE(2) + W_JA; double* mi = QM_WBC_BASE(2) + W_MISC;
-  double* A = QM_WBC_BASE(3) + W_A; double* bvec = QM_WBC_BASE(3) + W_B; double* D0 = QM_WBC_BASE(4) + W_D0; double* f0 = QM_WBC_BASE(4) + W_F0; double* v0 = f0 + MAXM;
-  double* Z = QM_WBC_BASE(5) + W_Z; double* Zn = QM_WBC_BASE(5) + W_ZN; double* AZ = QM_WBC_BASE(5) + W_AZ; double* DZ = QM_WBC_BASE(5) + W_DZ; double* K = QM_WBC_BASE(5) + W_K; double* G = QM_WBC_BASE(5) + W_G; double* Vh = QM_WBC_BASE(5) + W_VH;
-  double* xs = QM_WBC_BASE(6) + W_VEC; double* zs = xs + 36; double* gs = zs + 36; double* rds = gs + 36; double* rhs = rds + 36; double* dzs = rhs + 36;
-  double* fhat = QM_WBC_BASE(7) + (W_VEC + 6 * 36); double* lam = fhat + 56; double* wt = lam + 56; double* tzv = wt + 56; double* red = QM_WBC_BASE(8) + (W_VEC + 6 * 36 + 4 * 56); double* ctl = red + 1024;
+  double* in = carve + W_IN; double* rbd = in; double* xDes = in + 55; double* uDes = in + 85; double* il = in + 115;
+  double* qM = carve + W_Q; double* vM = qM + 24; double* qD = qM + 48; double* vD = qM + 72;
+  double* body = carve + W_BODY; double* dof = carve + W_DOF; double* wr = carve + W_WR; double* M = carve + W_M; double* nle = carve + W_NLE;
+  double* Jf = carve + W_JF; double* Ja = carve + W_JA; double* mi = carve + W_MISC;
+  double* A = carve + W_A; double* bvec = carve + W_B; double* D0 = carve + W_D0; double* f0 = carve + W_F0; double* v0 = f0 + MAXM;
+  double* Z = carve + W_Z; double* Zn = carve + W_ZN; double* AZ = carve + W_AZ; double* DZ = carve + W_DZ; double* K = carve + W_K; double* G = carve + W_G; double* Vh = carve + W_VH;
+  double* xs = carve + W_VEC; double* zs = xs + 36; double* gs = zs + 36; double* rds = gs + 36; double* rhs = rds + 36; double* dzs = rhs + 36;
+  double* fhat = carve + (W_VEC + 6 * 36); double* lam = fhat + 56; double* wt = lam + 56; double* tzv = wt + 56; double* red = carve + (W_VEC + 6 * 36 + 4 * 56); double* ctl = red + 1024;
 
   // Wavefront 0 solves the instance; the other three sit on the CU's idle SIMDs and take their share of the matrix-core tiles of the
   // interior point between two workgroup barriers (ipm_dev.h: ipmKTiles).  Command word: ctl[4] (0 = leave).
@@ -507,33 +484,11 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
   };
   if (wave != 0) {
     QM_LDS_BARRIER();                                     // inputs and coordinates (S1, S2) are in LDS
-#if QM_WBC_EXP == 3
-    if (wave == 2) desiredPass(lds + W_BODY2, lds + W_DOF2);     // experiment: the desired pass on helper wavefront 2 instead of 1
-#else
     if (wave == 1) desiredPass(lds + W_BODY2, lds + W_DOF2);
-#endif
-#if QM_WBC_EXP == 4
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // experiment: drain every outstanding memory operation before the fork-join loop
-#elif QM_WBC_EXP == 5
-    __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127);   // experiment: pure timing -- every helper arrives ~16 k cycles later
-#endif
     const QpIo hio{G, nullptr, nullptr, DZ, fhat, K, wt, zs, red, forkCmd, nullptr, nullptr};
-#if defined(QM_WBC_DUMP) && !defined(QMGPU_HOST_EMULATION)
-    int dbgIt = 0;
-#endif
     for (;;) {
       QM_LDS_BARRIER();
       const int op = int(forkCmd[0]);
-#if defined(QM_WBC_DUMP) && !defined(QMGPU_HOST_EMULATION)
-      // what each helper wavefront saw, in order: tail of checkpoint image (wave - 1): per iteration [op, exec lo, exec hi, wave, first active lane, job M, N, K]
-      if (blockIdx.x == 0 && dbgIt < 45) {
-        const unsigned long long ex = __builtin_amdgcn_read_exec();
-        double* o = qmk::qmWbcDump + ((wave - 1) * 17000 + 16640 + dbgIt * 8);
-        o[0] = double(op); o[1] = double(unsigned(ex)); o[2] = double(unsigned(ex >> 32)); o[3] = double(wave); o[4] = double(__builtin_amdgcn_readfirstlane(lane));
-        o[5] = forkJob[4]; o[6] = forkJob[5]; o[7] = forkJob[6];
-      }
-      ++dbgIt;
-#endif
       if (op == 0) break;
       if (op == 36) ipmKTiles<36, LDZ, LDK>(hio, wave, lane);
       else if (op == 20) ipmKTiles<20, LDZ, LDK>(hio, wave, lane);
@@ -689,7 +644,6 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
   QM_LDS_BARRIER();
   QM_LDS_BARRIER();
 
-  QM_WBC_CHECKPOINT(0);   // model, Jacobians, desired pass
   QM_TICK(3);
   // ================================================================== hierarchical QP
   int status = 0;
@@ -1042,10 +996,6 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
     }
     QM_WAVE_SYNC();
 
-#ifdef QMGPU_EMU_DEBUG
-    if (lane == 0 && inst == QMGPU_DEBUG_INST) { printf("EMU level %d r %d n %d b:", level, r, n); for (int i = 0; i < r; ++i) printf(" %.10g", bvec[i]); printf("\n"); }
-#endif
-    if (level == 0) QM_WBC_CHECKPOINT(1);   // task 0: A, b, D0, f0
     QM_TICK(5);
     // ---- reduced data: AZ = A Z (r x n), rhat = A x - b, DZ = D0 Z, fhat
     for (int e = lane; e < MAXR * LDZ; e += 64) AZ[e] = 0.0;
@@ -1059,7 +1009,6 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
     if (level == 0) { if (lane < m0) fhat[lane] = f0[lane]; } else marginsAtX();
     QM_WAVE_SYNC();
     QM_TICK(13);
-    if (level == 0) QM_WBC_CHECKPOINT(2);   // reduced data of level 0: AZ, DZ, fhat
     QM_TICK(6);
     // ---- the level's QP (qp_dev.h)
     bool strong = false; int passes = 0;
@@ -1074,7 +1023,6 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
 #ifdef QM_RICCATI_TIMING
     if (lane == 0 && inst < 256) qmk::qmRiccatiTicks[512 + inst * 4 + 1 + level] = (unsigned long long)passes;
 #endif
-    if (level == 0) QM_WBC_CHECKPOINT(3);   // z of level 0
     QM_TICK(7);
     // ---- x = x_prev + Z z (HoQp.h:31-34); the level's own variables stay in rds (the canonical representative is taken relative to them)
     double xn = 0.0;
@@ -1085,10 +1033,6 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
     // slack solution of task 0 (HoQp.cpp:152-158): v = max(0, D x - f), exactly
     if (level == 0 && lane < m0) { double s = -f0[lane]; for (int q = 0; q < ND; ++q) s += D0[lane * ND + q] * xs[q]; v0[lane] = fmax(0.0, s); }
     QM_WAVE_SYNC();
-#ifdef QMGPU_EMU_DEBUG
-    if (lane == 0 && inst == QMGPU_DEBUG_INST) { printf("EMU level %d passes %d status %d x:", level, passes, st); for (int i = 0; i < 36; ++i) printf(" %.10g", xs[i]); printf("\n"); }
-#endif
-    if (level == 0) QM_WBC_CHECKPOINT(4);   // x, v0 after level 0
     QM_TICK(8);
     // ---- Z <- Z kernel(A Z) (HoQp.cpp:126-133); A Z again where the implied equalities overwrote it
     if (hadEq) { for (int e = lane; e < MAXR * LDZ; e += 64) AZ[e] = 0.0; QM_WAVE_SYNC(); forkGemm(false, A, ND, Z, LDZ, r, n, ND, AZ, LDZ, 0.0); QM_WAVE_SYNC(); }
@@ -1120,8 +1064,6 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
     n = nNew;
     QM_WAVE_SYNC();
     QM_TICK(17);
-    if (level == 0) QM_WBC_CHECKPOINT(5);   // Z after the first null space
-    if (level == 1) QM_WBC_CHECKPOINT(6);
     // ---- canonical representative of the level (pass 1): min |z* + N w|^2 inside the inequality rows, i.e. task rows N (nOld x n), residual z* (rds); x += Z w
     if (canonical && n > 0) {
       double* AZc = level == 0 ? Zn : AZ;
@@ -1135,9 +1077,6 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
       unsigned long long wsWordC = wsLoad(pass, level, 1);
       const int stc = levelQp(AZc, nOld, rds, n, false, rowNonZero(n), eqRow, strongC, passesC, wsWordC, nullptr, false);
       wsStore(pass, level, 1, wsWordC, passesC);
-#ifdef QMGPU_EMU_DEBUG
-      if (lane == 0 && inst == QMGPU_DEBUG_INST) printf("EMU canonical representative of level %d: n %d rows %d passes %d status %d\n", level, n, nOld, passesC, stc);
-#endif
       if (stc != 0) status |= 8;
       double xc = 0.0;
       if (lane < ND) { xc = xs[lane]; for (int j = 0; j < n; ++j) xc += Z[lane * LDZ + j] * zs[j]; }
@@ -1150,7 +1089,6 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
   canonical = true;
   }
   QM_WAVE_SYNC();
-  QM_WBC_CHECKPOINT(7);
   QM_TICK(9);
   // ---- updateCmd (WbcBase.cpp:580-595): tau = [M_j, -J_j^T] x + h_j
   if (lane < ND) a.out[size_t(inst) * 54 + lane] = xs[lane];

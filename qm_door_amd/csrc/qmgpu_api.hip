@@ -280,15 +280,6 @@ int qmgpu_debug_ad_wg_clocks(unsigned long long* out64, int count) {
 }
 #endif
 
-#ifdef QM_WBC_DUMP
-// experiment build only (tools/wbc_variants.py): LDS images of instance 0 of the last wbc_kernel launch at the kernel's checkpoints
-extern "C" int qmgpu_debug_wbc_dump(double* out, int doubles) {
-  if (hipDeviceSynchronize() != hipSuccess) return QMGPU_ERR_HIP;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(qmk::qmWbcDump), sizeof(double) * size_t(doubles)) != hipSuccess) return QMGPU_ERR_HIP;
-  return QMGPU_OK;
-}
-#endif
-
 int qmgpu_debug_poison(qmgpu_handle h) {
   if (!h) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null handle");
   return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device);

@@ -62,16 +62,11 @@ def test_fp32_translation_unit_contains_no_fp64_arithmetic():
     the library boundary and mpc_init_kernel, which forms node times / steps / schedule phases from the caller's fp64 times."""
     import re
     import shutil
-    import subprocess
-    import tempfile
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not shutil.which(hipcc):
+    from qm_door_amd import build as qb
+    if not shutil.which(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")):
         pytest.skip("no hipcc")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     with tempfile.TemporaryDirectory() as tmp:
-        asm = os.path.join(tmp, "mpc32.s")
-        subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-DQM_REAL=float", "-Dqmk=qmk32", "--cuda-device-only", "-S",
-                               os.path.join(root, "qm_door_amd", "csrc", "qmgpu_mpc32.hip"), "-o", asm], stderr=subprocess.DEVNULL)
+        asm, = qb.device_asm(tmp, units=["mpc32"])      # compiled as the library ships it
         text = open(asm).read()
     kernels = {}
     for m in re.finditer(r"^(_ZN5qmk32\w+):.*?\n(.*?)^\.Lfunc_end\d+:", text, re.M | re.S):   # kernels and called device functions alike
@@ -99,7 +94,7 @@ def test_generated_device_structs_are_current():
 
 
 def test_inline_assembly_has_no_data_hazard_the_compiler_cannot_see():
-    """tools/check_asm_hazards.py on the device assembly of both translation units (hipcc cross-compiles here): the DPP multiply-adds written as
+    """tools/check_asm_hazards.py on the device assembly of every translation unit the library ships (hipcc cross-compiles here): the DPP multiply-adds written as
     inline assembly (gpu_rt.h: qmFmacRowBcast) must not read a source register a VALU instruction wrote in the two preceding wait states."""
     import subprocess, sys
     r = subprocess.run([sys.executable, os.path.join(S.ROOT, "tools", "check_asm_hazards.py"), "--build"], capture_output=True, text=True, timeout=900)

@@ -178,7 +178,7 @@ def test_emu_first_level_of_a_diverged_robot_goes_through_the_interior_point(emu
     a = (d["xd"][i], d["ud"][i], d["rbd"][i], int(d["mode"][i]), float(d["period"][i]), float(d["time"][i]))
     s_now, now, _ = orc.wbc_update(*a, d["il"][i].copy())
     try:
-        orc.set_experiment(own_interior_point=0)
+        orc.set_experiment(own_interior_point=False)
         s_cold, cold, _ = orc.wbc_update(*a, d["il"][i].copy())
     finally:
         orc.set_experiment()

@@ -143,7 +143,7 @@ def test_hip_against_the_50_digit_solution_of_the_reference_qp(interface, oracle
 
 def test_first_level_behind_the_interior_point_ends_at_the_cold_vertex(oracle):
     """tests/golden/wbc_slow_ticks.npz (the ten slowest WBC ticks of round 6's steady-state leg: robots whose torque limits cannot hold): the first level through the interior
-    point with its own rows as penalised slacks (default) against the same level cold from z = 0 (own_interior_point = 0, the algorithm until round 6): same torques,
+    point with its own rows as penalised slacks (default) against the same level cold from z = 0 (own_interior_point = False, the algorithm until round 6): same torques,
     a bounded number of passes instead of up to 46 working-set changes."""
     d = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wbc_slow_ticks.npz"))
     n = len(d["mode"])
@@ -159,7 +159,7 @@ def test_first_level_behind_the_interior_point_ends_at_the_cold_vertex(oracle):
         oracle.set_working_set(None)
         return np.array(outs), np.array(passes)
     try:
-        oracle.set_experiment(own_interior_point=0)
+        oracle.set_experiment(own_interior_point=False)
         cold, p_cold = run()
     finally:
         oracle.set_experiment()
@@ -172,7 +172,7 @@ def test_first_level_behind_the_interior_point_ends_at_the_cold_vertex(oracle):
 @pytest.mark.parametrize("variant", [0, 1])
 def test_first_level_paths_agree_on_fast_robots(oracle, interface, variant):
     """support.wbc_fast_robots_batch (128 instances): robots moving so fast that the first level's limits cannot hold.  The default path (held-variable form for at most four
-    iterations, then the interior point with the own rows as penalised slacks) and the cold path (own_interior_point = 0) end at the same torques; a third of the instances
+    iterations, then the interior point with the own rows as penalised slacks) and the cold path (own_interior_point = False) end at the same torques; a third of the instances
     take the new path."""
     b = S.wbc_fast_robots_batch(interface, variant, 128)
 
@@ -187,7 +187,7 @@ def test_first_level_paths_agree_on_fast_robots(oracle, interface, variant):
         oracle.set_working_set(None)
         return np.array(outs), np.array(passes)
     try:
-        oracle.set_experiment(own_interior_point=0)
+        oracle.set_experiment(own_interior_point=False)
         cold, p_cold = run()
     finally:
         oracle.set_experiment()

@@ -112,7 +112,7 @@ def test_first_level_of_diverged_robots_goes_through_the_interior_point(interfac
     """tests/golden/wbc_slow_ticks.npz: the ten slowest WBC ticks of round 6's steady-state leg -- robots whose plan has diverged, the first level's minimum-norm point
     violates 7-16 limits.  Until the end of round 6 three of them took 23-46 working-set changes of a 36-variable level from z = 0 (3.1-3.5 ms, the tail of every
     256-instance launch they were in).  Now a held-variable form that is rejected, or still running after QP_HELD_CAP iterations, hands the level to the interior point with the
-    own rows as penalised slacks: same vertex (the CPU restatement's cold path is the reference here: own_interior_point = 0), a bounded number of passes."""
+    own rows as penalised slacks: same vertex (the CPU restatement's cold path is the reference here: own_interior_point = False), a bounded number of passes."""
     import os
     import gpu_harness as G
     d = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wbc_slow_ticks.npz"))
@@ -123,7 +123,7 @@ def test_first_level_of_diverged_robots_goes_through_the_interior_point(interfac
     r = wb.results()
     assert (r["status"] == 0).all()
     passes = np.ascontiguousarray(r["working_set"][:, 13:15]).view(np.uint8).astype(int) & 127
-    oracle.set_experiment(own_interior_point=0)      # cold from z = 0, as until round 6
+    oracle.set_experiment(own_interior_point=False)      # cold from z = 0, as until round 6
     try:
         cold = np.array([oracle.wbc_update(d["xd"][i], d["ud"][i], d["rbd"][i], int(d["mode"][i]), float(d["period"][i]), float(d["time"][i]), d["il"][i].copy())[1] for i in range(n)])
     finally:
@@ -139,7 +139,7 @@ def test_first_level_of_diverged_robots_goes_through_the_interior_point(interfac
 @pytest.mark.parametrize("variant", [0, 1])
 def test_wbc_fast_robots_whose_limits_cannot_hold(interface, variant):
     """support.wbc_fast_robots_batch (512 instances, every contact mode, both controllers): joint rates of +-15 rad/s -- the first level's limits cannot hold, 40 % of the instances
-    go through the interior point with the own rows as penalised slacks.  GPU against the oracle on the same path and against the oracle's cold path (own_interior_point = 0,
+    go through the interior point with the own rows as penalised slacks.  GPU against the oracle on the same path and against the oracle's cold path (own_interior_point = False,
     the algorithm until round 6): status words zero, every block within 1e-9, first-level passes bounded."""
     import gpu_harness as G
     B = 512
@@ -155,7 +155,7 @@ def test_wbc_fast_robots_whose_limits_cannot_hold(interface, variant):
     ref, st = w["out"], w["status"]
     assert (st == 0).all()
     try:
-        orc.set_experiment(own_interior_point=0)
+        orc.set_experiment(own_interior_point=False)
         w = orc.wbc_batch(c["xd"], c["u"], c["rbd"], c["mode"], 0.002, c["t"], c["il"], variant=variant)
         cold, st_c = w["out"], w["status"]
     finally:

@@ -7,16 +7,16 @@ operand arrives through a "v" constraint: when the value lives in an accumulatio
 spilled, the register allocator materialises it with v_accvgpr_read / a reload IMMEDIATELY in front of the asm statement.
 
   python tools/check_asm_hazards.py file.s [...]      # device assembly (hipcc -S --offload-device-only)
-  python tools/check_asm_hazards.py --build           # compiles both translation units of the product (+ every variant of tests/build_variants.py) and checks them
+  python tools/check_asm_hazards.py --build [-D...]   # compiles every device translation unit of the product (qm_door_amd/build.py: device_asm), with the given extra flags, and checks them
 
 Exit status 1 if a hazard is found.  tests/test_abi.py runs it on the product sources (CPU test: hipcc cross-compiles here)."""
 import os
 import re
-import subprocess
 import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 REG = re.compile(r"\b([va])(\d+)\b|\b([va])\[(\d+):(\d+)\]")
 
 
@@ -79,25 +79,12 @@ def check(path, verbose=False):
     return n, found
 
 
-def build_asm(out_dir, extra=()):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    csrc = os.path.join(ROOT, "qm_door_amd", "csrc")
-    ipra = [] if any(str(f).startswith("-enable-ipra") for f in extra) else ["-mllvm", "-enable-ipra=0"]   # as qm_door_amd/build.py
-    base = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", *ipra, "--offload-device-only", "-S", *extra]
-    jobs = [(base + [os.path.join(csrc, "qmgpu_api.hip"), "-o", os.path.join(out_dir, "api.s")]),
-            (base + ["-DQM_REAL=float", "-Dqmk=qmk32", os.path.join(csrc, "qmgpu_mpc32.hip"), "-o", os.path.join(out_dir, "mpc32.s")])]
-    procs = [subprocess.Popen(j, stderr=subprocess.DEVNULL) for j in jobs]
-    for p, j in zip(procs, jobs):
-        if p.wait() != 0:
-            raise subprocess.CalledProcessError(p.returncode, j)
-    return [j[-1] for j in jobs]
-
-
 def main(argv):
     files = [a for a in argv if not a.startswith("-")]
     if "--build" in argv:
+        from qm_door_amd import build as qb
         tmp = tempfile.mkdtemp(prefix="qm_asm_")
-        files += build_asm(tmp, tuple(a for a in argv if a.startswith("-D") or a.startswith("-O") or a.startswith("-m") or a.startswith("-f")))
+        files += qb.device_asm(tmp, tuple(a for a in argv if a.startswith("-D") or a.startswith("-O") or a.startswith("-m") or a.startswith("-f")))
     bad = 0
     for p in files:
         n, found = check(p)

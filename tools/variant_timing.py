@@ -1,5 +1,5 @@
 """Per-kernel times of the bench workload (256 instances, N = 100) for build variants of the library (tools/wbc_variants.py) next to the product build.
-    python tools/variant_timing.py s_maxilp s_iterilp      # on the GPU box; the variants must have been built (wbc_variants.py --build ...)"""
+    python tools/variant_timing.py o2 noinl      # on the GPU box; the variants must have been built (wbc_variants.py --build ...)"""
 import os, sys, numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))

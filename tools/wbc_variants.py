@@ -34,90 +34,12 @@ VARIANTS = {
     #  semantics at the hand-off are whatever this LLVM gives it; the product states them -- fence release / barrier / fence acquire -- and does not depend on that.  Kept buildable.)
     "bare": (("-DQM_WAVE_SYNC_BARE",), False, "round 2's QM_WAVE_SYNC (bare wave barrier, no fences): NOT a build that has to agree since round 6"),
     "ipra": (("-mllvm", "-enable-ipra=1"), True, "interprocedural register allocation on (LLVM's default for AMDGPU; rounds 1-2 shipped this)"),
-    "opq_noipra": (("-DQM_WBC_OPAQUE_MASK=511",), True, "whole LDS carve of wbc_kernel behind one opaque address-space-3 base: wrong torques with IPRA on (round 2), correct with it off"),
-    "opq": (("-DQM_WBC_OPAQUE_MASK=511", "-mllvm", "-enable-ipra=1"), False, "round 2's failing experiment (REPRODUCER: returns wrong torques): opaque LDS base + IPRA on"),
+    "opq_noipra": (("-DQM_WBC_OPAQUE_LDS",), True, "whole LDS carve of wbc_kernel behind one opaque address-space-3 base: wrong torques with IPRA on (round 2), correct with it off"),
+    "opq": (("-DQM_WBC_OPAQUE_LDS", "-mllvm", "-enable-ipra=1"), False, "round 2's failing experiment (REPRODUCER: returns wrong torques): opaque LDS base + IPRA on"),
+    "qptrace": (("-DQM_QP_TRACE=0",), False, "device printf of instance 0's level-solver iterations (experiments: tools/wbc_variants.py --build qptrace, then a batch of one through that library)"),
 }
-# bisection of the failing mask (wbc_kernel.h: nine array groups): coarse groups {inputs+coordinates, task arrays, vectors} = bits 0,1 | 3,4 | 6,7,8 fail
-# together; F = that set, F minus one fine group each
-_F = 0b111011011
-VARIANTS["f_all"] = (("-DQM_WBC_OPAQUE_MASK=%d" % _F, "-mllvm", "-enable-ipra=1"), False, "groups {inputs, coordinates, tasks, vectors} opaque, IPRA on: correct (the failure needs four of the five coarse groups)")
-
-
-_OPQ = ("-DQM_WBC_OPAQUE_MASK=511", "-mllvm", "-enable-ipra=1")   # the failing combination; each experiment below changes ONE thing
-VARIANTS["x_inline"] = ((*_OPQ, "-DQM_WBC_EXP=2"), False, "failing combination, bodyPass inlined (no call on the helper wavefront's extra path): correct")
-VARIANTS["x_wave2"] = ((*_OPQ, "-DQM_WBC_EXP=3"), False, "failing combination, desired pass on helper wavefront 2: fails too (the failure follows the call)")
-VARIANTS["x_drain"] = ((*_OPQ, "-DQM_WBC_EXP=4"), False, "failing combination, s_waitcnt vmcnt(0) lgkmcnt(0) before the fork-join loop: still fails (not memory ordering)")
-VARIANTS["x_sleep"] = ((*_OPQ, "-DQM_WBC_EXP=5"), False, "failing combination, helpers sleep before the fork-join loop: still fails (not timing)")
-# timing experiments (tools/variant_timing.py): the instruction scheduler's strategy for the whole translation unit
-VARIANTS["qptrace"] = (("-DQM_QP_TRACE=0",), False, "device printf of instance 0's level-solver iterations (experiments: tools/wbc_variants.py --build qptrace, then a batch of one through that library)")
-VARIANTS["s_maxilp"] = (("-mllvm", "-amdgpu-sched-strategy=max-ilp"), False, "LLVM's max-ILP scheduling strategy (timing experiment)")
-VARIANTS["s_iterilp"] = (("-mllvm", "-amdgpu-sched-strategy=iterative-ilp"), False, "LLVM's iterative ILP scheduling strategy (timing experiment)")
-VARIANTS["s_maxmem"] = (("-mllvm", "-amdgpu-sched-strategy=max-memory-clause"), False, "LLVM's max-memory-clause scheduling strategy (timing experiment)")
-VARIANTS["s_track"] = (("-mllvm", "-amdgpu-use-amdgpu-trackers"), False, "AMDGPU register-pressure trackers in the scheduler (timing experiment)")
-VARIANTS["s_bias0"] = (("-mllvm", "-amdgpu-schedule-metric-bias=0"), False, "scheduler metric bias 0: latency over occupancy (timing experiment)")
-VARIANTS["s_bias100"] = (("-mllvm", "-amdgpu-schedule-metric-bias=100"), False, "scheduler metric bias 100: occupancy only (timing experiment)")
-VARIANTS["s_relax"] = (("-mllvm", "-amdgpu-schedule-relaxed-occupancy"), False, "relaxed occupancy targets (timing experiment)")
-VARIANTS["s_nopost"] = (("-mllvm", "-enable-post-misched=0"), False, "no post-RA machine scheduler (timing experiment)")
-VARIANTS["s_nounroll"] = (("-fno-unroll-loops",), False, "no loop unrolling beyond the pragmas (timing experiment)")
-VARIANTS["dump"] = (("-DQM_WBC_DUMP",), False, "product + LDS dump checkpoints of instance 0")
-VARIANTS["dump_opq"] = (("-DQM_WBC_DUMP", "-DQM_WBC_OPAQUE_MASK=511", "-mllvm", "-enable-ipra=1"), False, "failing combination + LDS dump checkpoints (the instrumentation of the helper loop hides the failure)")
-
-# LDS carve of wbc_kernel.h (doubles), for naming what differs between two dumps
-CARVE = {'IN': 0, 'Q': 160, 'BODY': 256, 'DOF': 896, 'WR': 1040, 'M': 1160, 'NLE': 1736, 'JF': 1760, 'JA': 2048, 'MISC': 2192, 'A': 2336, 'B': 3128, 'D0': 3152, 'F0': 5168, 'Z': 5280,
-         'ZN': 6612, 'AZ': 7944, 'DZ': 8758, 'K': 10830, 'G': 12162, 'VH': 13494, 'VEC(x z g rd rhs dz)': 14374, 'fhat lam wt tz': 14590, 'red': 14814, 'ctl': 15838, 'BODY2': 15846, 'DOF2': 16486,
-         'END': 16630}
-CHECKPOINTS = ["0 model", "1 task0 assembled", "2 reduced data L0", "3 after ipm L0", "4 x after L0", "5 Z after null space 0", "6 after null space 1", "7 end"]
-
-
-def dump_of(lib):
-    """runs the WBC alone (bench scenario, B = 64, from the oracle-free inputs of cycle_all_modes) and returns the LDS images of instance 0"""
-    import ctypes as C
-    import torch
-    import bench
-    import gpu_harness as G
-    from qm_door_amd import api
-    itf = api.QMInterface(lib=lib)
-    B, N = 64, 20
-    sc = bench.build_scenario(itf, B, seed=1)
-    sol = G.make_solver(itf, B, N)
-    mb = G.MpcBatch(sc["x0"], sc["tt"], sc["ts"], np.full(B, sc["nev"], dtype=np.int32), np.tile(sc["ev"], (B, 1)), np.tile(sc["md"], (B, 1)), N)
-    wb = G.WbcBatch(sc["rbd"], np.full(B, 0.002), np.full(B, 20.0), np.zeros((B, 30)))
-    sol.cycle(mb.args, G.dev(np.zeros(B), torch.float64), wb.args)
-    w = wb.results()
-    n = 8 * 17000
-    buf = np.zeros(n)
-    lib.qmgpu_debug_wbc_dump.argtypes = [C.c_void_p, C.c_int]
-    assert lib.qmgpu_debug_wbc_dump(buf.ctypes.data_as(C.c_void_p), n) == 0
-    sol.close()
-    img = buf.reshape(8, 17000)
-    for wv in range(3):   # what the helper wavefronts saw: [op, exec lo, exec hi, wave, first active lane, job M, N, K] per loop iteration
-        rec = img[wv, 16640:17000].reshape(45, 8)
-        print("  helper wavefront %d:" % (wv + 1))
-        for it in range(8):
-            r = rec[it]
-            print("     it %d: op %d exec %08x%08x wave %d first lane %d job M N K = %d %d %d" % (it, r[0], int(r[2]), int(r[1]), r[3], r[4], r[5], r[6], r[7]))
-    return img[:, :CARVE["END"]], w
-
-
-def compare_dumps(a_name, b_name):
-    from qm_door_amd import abi
-    da, wa = dump_of(abi.load_library(lib_path(a_name)))
-    db, wb_ = dump_of(abi.load_library(lib_path(b_name)))
-    print("status", a_name, int((wa["status"] != 0).sum()), b_name, int((wb_["status"] != 0).sum()))
-    names = list(CARVE.items())
-    for cp in range(8):
-        diffs = []
-        for (nm, lo), (_, hi) in zip(names[:-1], names[1:]):
-            x, y = da[cp, lo:hi], db[cp, lo:hi]
-            both_nan = np.isnan(x) & np.isnan(y)
-            bad = ~both_nan & ~(x == y)
-            if bad.any():
-                idx = np.flatnonzero(bad)
-                diffs.append("%s: %d of %d differ, first at +%d (%.6g vs %.6g), max |d| %.3g" % (nm, bad.sum(), hi - lo, idx[0], x[idx[0]], y[idx[0]], np.nanmax(np.abs(np.nan_to_num(x[bad]) - np.nan_to_num(y[bad])))))
-        print("checkpoint", CHECKPOINTS[cp], "--", "identical" if not diffs else "")
-        for d in diffs:
-            print("     ", d)
-    np.savez(os.path.join(ROOT, "gpurun_out", "wbc_dumps.npz"), a=da, b=db)
+# (the round-2 bisection of the failing build -- per-group opaque masks, bodyPass inlined, the desired pass on wavefront 2, a drain, a sleep --, the LDS dumps that
+#  located it and the scheduler timing experiments of tools/variant_timing.py live at commit 699c486; DESIGN.md section 4.7 and profiles/ have their results)
 
 
 def lib_path(name):
@@ -258,11 +180,9 @@ def run(names):
 
 def asm(names):
     import check_asm_hazards as H
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from qm_door_amd import build as qb
     for n in names:
-        d = os.path.join(VDIR, n, "asm")
-        os.makedirs(d, exist_ok=True)
-        for f in H.build_asm(d, VARIANTS[n][0]):
+        for f in qb.device_asm(os.path.join(VDIR, n, "asm"), VARIANTS[n][0]):
             cnt, found = H.check(f)
             print(n, os.path.basename(f), cnt, "DPP instructions,", len(found), "hazards")
 
@@ -276,5 +196,3 @@ if __name__ == "__main__":
         asm(names)
     if "--run" in sys.argv:
         run(names)
-    if "--dumps" in sys.argv:
-        compare_dumps(names[0], names[1])

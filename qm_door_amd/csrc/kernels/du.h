@@ -123,7 +123,6 @@ template <class T> struct Mat3 {
 };
 template <class T> __device__ __forceinline__ Vec3<T> mul(const Mat3<T>& R, real x, real y, real z) { return scale(x, R.c0) + scale(y, R.c1) + scale(z, R.c2); }
 template <class A, class B> __device__ __forceinline__ Vec3<ProdT<A, B>> mul(const Mat3<A>& R, Vec3<B> v) { return v.x * R.c0 + v.y * R.c1 + v.z * R.c2; }
-template <class A, class B> __device__ __forceinline__ Vec3<ProdT<A, B>> mulT(const Mat3<A>& R, Vec3<B> v) { return Vec3<ProdT<A, B>>(dot(R.c0, v), dot(R.c1, v), dot(R.c2, v)); }
 
 // symmetric 3x3: xx xy xz yy yz zz
 template <class T> struct Sym3 {

@@ -2,7 +2,7 @@
 //   rbdState[55] -> centroidal state x[30] (QMController::updateStateEstimation, qm_controllers/src/QMController.cpp:239-244) and
 //   command -> two-knot TargetTrajectories (qm_controllers/src/QmTargetTrajectoriesPublisher_node.cpp:59-254).
 // The normalised centroidal momentum comes from the same streaming tree sweep as the flow map, run in the opposite direction:
-// the measured base twist is given, h is the unknown (closeSweep solves for the twist given h).
+// the measured base twist is given, h is the unknown (closeSweep2 solves for the twist given h).
 #pragma once
 #include "../../../include/qmgpu.h"
 #include "model_dev.h"

@@ -30,11 +30,10 @@ __device__ __forceinline__ int qmLoWord(double v) { return __double2loint(v); }
 __device__ __forceinline__ int qmHiWord(double v) { return __double2hiint(v); }
 __device__ __forceinline__ int qmLoWord(float v) { return __float_as_int(v); }
 __device__ __forceinline__ int qmHiWord(float) { return 0; }
-// butterfly exchange inside one wavefront; the trailing pointer argument of the cross-lane primitives is unused on the GPU (the host
-// emulation of tests/emu once exchanged through it)
-__device__ __forceinline__ real qmShflXor(real v, int mask, real* = nullptr) { return __shfl_xor(v, mask, 64); }
+// butterfly exchange inside one wavefront
+__device__ __forceinline__ real qmShflXor(real v, int mask) { return __shfl_xor(v, mask, 64); }
 // value of lane `src` (wave-uniform, compile-time constant after unrolling) broadcast through SGPRs: v_readlane_b32 per word
-__device__ __forceinline__ real qmReadLane(real v, int src, real* = nullptr) {
+__device__ __forceinline__ real qmReadLane(real v, int src) {
   const int lo = __builtin_amdgcn_readlane(qmLoWord(v), src);
   const int hi = sizeof(real) == 8 ? __builtin_amdgcn_readlane(qmHiWord(v), src) : 0;
   return qmFromWords(lo, hi, real());
@@ -57,11 +56,9 @@ template <class T> struct QmAccOf { typedef QmAccD type; };
 template <> struct QmAccOf<float> { typedef QmAccF type; };
 typedef QmAccOf<real>::type QmAcc;
 typedef real QmD2 __attribute__((ext_vector_type(2)));   // load/store unit of the register-staged prefetch (a native vector: stays in registers, unlike HIP's double2 struct)
-__device__ __forceinline__ void qmMfma(QmAccD& c, double a, double b, double* = nullptr) { c = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ void qmMfma(QmAccF& c, float a, float b, float* = nullptr) { c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ void qmMfma(QmAccD& c, double a, double b) { c = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ void qmMfma(QmAccF& c, float a, float b) { c = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ constexpr int qmARow(int p) { return sizeof(real) == 8 ? p : (p >> 2) + 4 * (p & 3); }
-__device__ __forceinline__ double qmRsqrt(double x) { return rsqrt(x); }
-__device__ __forceinline__ float qmRsqrt(float x) { return rsqrtf(x); }
 // a * b and a - b rounded on their own: the optimiser may not fuse them into one multiply-add (results that feed exact comparisons shared with the host oracle)
 __device__ __forceinline__ double qmMulNoFma(double a, double b) { return __dmul_rn(a, b); }
 __device__ __forceinline__ double qmSubNoFma(double a, double b) { return __dsub_rn(a, b); }
@@ -83,24 +80,23 @@ __device__ __forceinline__ float qmRcpPos(float x) { return __builtin_amdgcn_rcp
 // acc += (bc of lane R of this lane's row of 16 lanes) * m in ONE instruction (DPP row_newbcast, legal on 64-bit operands since gfx90a):
 // the multiplier broadcast of a row operation without the v_readlane pair + wait state + separate multiply-add.  FIRST puts the two wait
 // states a DPP source needs after a VALU write in front (the hazard recogniser does not look into inline assembly).
-template <int R, bool FIRST> __device__ __forceinline__ void qmFmacRowBcast(double& acc, double bc, double m, double* = nullptr) {
+template <int R, bool FIRST> __device__ __forceinline__ void qmFmacRowBcast(double& acc, double bc, double m) {
   if (FIRST) asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(bc), "v"(m), "n"(R));
   else asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(bc), "v"(m), "n"(R));
 }
-template <int R, bool FIRST> __device__ __forceinline__ void qmFmacRowBcast(float& acc, float bc, float m, float* = nullptr) {
+template <int R, bool FIRST> __device__ __forceinline__ void qmFmacRowBcast(float& acc, float bc, float m) {
   if (FIRST) asm volatile("s_nop 1\n\tv_fmac_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(bc), "v"(m), "n"(R));
   else asm volatile("v_fmac_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(bc), "v"(m), "n"(R));
 }
 // the value of lane 16 G + (lane & 15) in every lane: one row of 16 lanes replicated into all four (ds_bpermute: the LDS crossbar, no LDS memory)
-template <int G> __device__ __forceinline__ real qmReplicateRow(real v, real* = nullptr) {
+template <int G> __device__ __forceinline__ real qmReplicateRow(real v) {
   const int addr = (16 * G + (int(threadIdx.x) & 15)) * 4;
   const int lo = __builtin_amdgcn_ds_bpermute(addr, qmLoWord(v));
   const int hi = sizeof(real) == 8 ? __builtin_amdgcn_ds_bpermute(addr, qmHiWord(v)) : 0;
   return qmFromWords(lo, hi, real());
 }
-__device__ __forceinline__ real qmReplicateRow0(real v, real* s = nullptr) { return qmReplicateRow<0>(v, s); }
+__device__ __forceinline__ real qmReplicateRow0(real v) { return qmReplicateRow<0>(v); }
 // pointer to LDS that keeps its address space through a function call (a generic pointer to LDS compiles to flat loads)
-#define QM_LDS_CONST_PTR(T) const T __attribute__((address_space(3)))*
 #define QM_TO_LDS_PTR(T, p) ((const T __attribute__((address_space(3)))*)(p))
 // Read-only problem data (model, settings, constant weight matrices) seen through the CONSTANT address space.  A kernel that has stored to global memory can
 // no longer prove that a later load from a plain global pointer is unclobbered, so the backend fetches even wave-uniform constants with VECTOR loads
@@ -115,12 +111,8 @@ template <class T> __device__ __forceinline__ const T* qmConstantPtr(const T* p)
   return (const T*)p4;
 }
 #define QM_CONSTANT_REF(T, lvalue) (*qmk::qmConstantPtr<T>(&(lvalue)))
-#define QM_CONSTANT_PTR(T, ptr) (qmk::qmConstantPtr<T>(ptr))
 // streaming store: data written once and not read again by this kernel (goes out with the non-temporal cache policy)
 #define QM_STREAM_STORE(ptr, value) __builtin_nontemporal_store((value), (ptr))
-#define QM_STREAM_LOAD(ptr) __builtin_nontemporal_load(ptr)   // read once, never again by this CU
-// a load that is served by the L2 and does not allocate in the CU's vector L1 (agent-scope relaxed atomic load: global_load ... sc1)
-#define QM_L2_LOAD(ptr) __hip_atomic_load((ptr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 // keeps a value in a register at this point: loads placed before it stay unconditional (the compiler otherwise sinks an LDS read
 // into the select that consumes it and pays the LDS latency once per branch)
 #define QM_KEEP(x) asm volatile("" : "+v"(x))
@@ -128,20 +120,12 @@ template <class T> __device__ __forceinline__ const T* qmConstantPtr(const T* p)
 // instruction.  With the address known at compile time (dynamic LDS starts at a link-time constant) a fully unrolled loop materialises a
 // separate address per access in a scalar register, spills them into vector lanes and pays v_readlane + v_mov per LDS instruction.
 #define QM_OPAQUE_LDS(T, name, p) T __attribute__((address_space(3)))* name = (T __attribute__((address_space(3)))*)(p); asm volatile("" : "+v"(name))
-// upper-triangle tile set of a symmetric product: acc[(ti,tj), ti <= tj] += A_ti B_tj for one k step of 4
-template <int TP> __device__ __forceinline__ void qmMfmaUpper(QmAcc* acc, const real* a, const real* b, real* = nullptr) {
-  int t = 0;
-#pragma unroll
-  for (int ti = 0; ti < TP; ++ti)
-#pragma unroll
-    for (int tj = ti; tj < TP; ++tj, ++t) qmMfma(acc[t], a[ti], b[tj]);
-}
 // "every lane's value, addressable by (compile-time) lane index": v_readlane at the point of use
 struct QmGather {
   real v;
   __device__ __forceinline__ real get(int src) const { return qmReadLane(v, src); }
 };
-__device__ __forceinline__ QmGather qmGather(real v, real* = nullptr) { return QmGather{v}; }
+__device__ __forceinline__ QmGather qmGather(real v) { return QmGather{v}; }
 // wavefront all-reduces (butterfly: every lane ends with the same value, bit for bit -- the operation is commutative and both
 // partners of a step combine the same pair).  Steps 1, 2 (quad permutes), 4 (row_half_mirror: quads are uniform by then) and 8
 // (row_mirror) are DPP moves, steps 16 and 32 the row / half-wave swaps of gfx950 (v_permlane16_swap, v_permlane32_swap): ~25
@@ -173,9 +157,9 @@ template <class Op> __device__ __forceinline__ real qmAllReduce(real v, Op op) {
   v = op(v, qmHalfXor32(v, (lane & 32) != 0));
   return v;
 }
-__device__ __forceinline__ real qmAllSum(real v, real* = nullptr) { return qmAllReduce(v, [](real a, real b) { return a + b; }); }
-__device__ __forceinline__ real qmAllMax(real v, real* = nullptr) { return qmAllReduce(v, [](real a, real b) { return fmax(a, b); }); }
-__device__ __forceinline__ real qmAllMin(real v, real* = nullptr) { return qmAllReduce(v, [](real a, real b) { return fmin(a, b); }); }
+__device__ __forceinline__ real qmAllSum(real v) { return qmAllReduce(v, [](real a, real b) { return a + b; }); }
+__device__ __forceinline__ real qmAllMax(real v) { return qmAllReduce(v, [](real a, real b) { return fmax(a, b); }); }
+__device__ __forceinline__ real qmAllMin(real v) { return qmAllReduce(v, [](real a, real b) { return fmin(a, b); }); }
 }  // namespace qmk
 using qmk::QmAcc; using qmk::QmD2; using qmk::QmGather;
 // Workgroup barrier that orders LDS traffic only: waits for this wavefront's LDS operations, then s_barrier.  Unlike

@@ -41,15 +41,6 @@ static_assert(LQ_LDS_DOUBLES * sizeof(real) <= 20480, "eight nodes per CU");
 // Both kernels of this file run one wavefront per workgroup: LDS hand-offs between lanes need no hardware barrier (a wavefront's
 // LDS operations complete in issue order), only the compiler fence QM_WAVE_SYNC() -- and, unlike __syncthreads(), that does not
 // wait for the global stores of the stage record that are still in flight.
-// dot product of a broadcast LDS row with a register vector, three independent FMA chains (one wavefront per SIMD: the fp64 FMA
-// latency is hidden by instruction-level parallelism only)
-__device__ __forceinline__ real dot30(const real* row, const real (&z)[30]) {
-  real s0 = 0.0_r, s1 = 0.0_r, s2 = 0.0_r;
-#pragma unroll
-  for (int i = 0; i < 30; i += 3) { s0 += row[i] * z[i]; s1 += row[i + 1] * z[i + 1]; s2 += row[i + 2] * z[i + 2]; }
-  return s0 + s1 + s2;
-}
-
 __device__ __forceinline__ real waveSum(real* red, int lane, real v) {
   red[lane] = v;
   QM_WAVE_SYNC();
@@ -443,7 +434,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         real v[18];
         real n2a = 0.0_r, n2b = 0.0_r;
 #pragma unroll
-        for (int i = k; i < 18; ++i) { v[i] = qmReadLane(qcol[i], k, red); if ((i - k) & 1) n2b += v[i] * v[i]; else n2a += v[i] * v[i]; }
+        for (int i = k; i < 18; ++i) { v[i] = qmReadLane(qcol[i], k); if ((i - k) & 1) n2b += v[i] * v[i]; else n2a += v[i] * v[i]; }
         // reflector v = column - alpha e_k, alpha = -sign(d_k) |column|; beta = 2 / v^T v = 1 / (|column| |v_k|): one reciprocal square root and one
         // reciprocal on the dependent chain of the step (a square root and an IEEE division before: ~28 dependent instructions)
         const real dk = v[k], n2 = n2a + n2b;
@@ -478,8 +469,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
       if (i < nv) {   // (wave uniform: trot has 8 velocity rows, stance 12)
         real sacc = ce[i];
 #pragma unroll
-        for (int k = 0; k < i; ++k) sacc -= qmReadLane(qcol[k], i, red) * y[k];
-        y[i] = sacc * qmReadLane(rinv, i, red);
+        for (int k = 0; k < i; ++k) sacc -= qmReadLane(qcol[k], i) * y[k];
+        y[i] = sacc * qmReadLane(rinv, i);
       }
     }
     // publish Y (rows k < 16, my column) and Q_v (lane 16 + c holds row c; rows 18..31 cleared) in region X
@@ -505,7 +496,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
       const int kk = 4 * ks + h;
       const real a0 = -Qs[la * LDQ + kk], a1 = -Qs[(16 + la) * LDQ + kk];
       const real b0 = Ym[kk * LDY + l16], b1 = Ym[kk * LDY + 16 + l16];
-      qmMfma(pc[0], a0, b0, red); qmMfma(pc[1], a0, b1, red); qmMfma(pc[2], a1, b0, red); qmMfma(pc[3], a1, b1, red);
+      qmMfma(pc[0], a0, b0); qmMfma(pc[1], a0, b1); qmMfma(pc[2], a1, b0); qmMfma(pc[3], a1, b1);
     }
     // Pall: rows 0..11 (forces): Px = 0, Pu = unit columns of the free stance forces -- neither is stored (layout.h) --, Pe = pinned swing forces;
     //       rows 12..29 (joint velocities): [Px | Pe] from the tiles, Pu = Q_v2 (record and LDS)
@@ -579,7 +570,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         pallOps(pb, tn);
         // columns 0..15 of the force rows of Pall (k steps 0..2) are zero: Px = 0 there, Pe is column 30, Pu starts at column 32
 #pragma unroll
-        for (int ks = (tn == 0 ? 3 : 0); ks < 8; ++ks) qmMfma(c1[tn], ab[ks], pb[ks], red);
+        for (int ks = (tn == 0 ? 3 : 0); ks < 8; ++ks) qmMfma(c1[tn], ab[ks], pb[ks]);
       }
     }
 #pragma unroll
@@ -645,7 +636,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
           real pb[8];
           pallOps(pb, tn);
 #pragma unroll
-          for (int ks = (tn == 0 ? 3 : 0); ks < 8; ++ks) { qmMfma(wA, r0[ks], pb[ks], red); qmMfma(wB, r1[ks], pb[ks], red); }   // (force rows of Pall: zero in columns 0..15)
+          for (int ks = (tn == 0 ? 3 : 0); ks < 8; ++ks) { qmMfma(wA, r0[ks], pb[ks]); qmMfma(wB, r1[ks], pb[ks]); }   // (force rows of Pall: zero in columns 0..15)
         }
         QM_WAVE_SYNC();   // the previous tile's readers are done
 #pragma unroll
@@ -690,7 +681,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             const int qq = 4 * ks + h;
             const bool on = qq < 6;
             const real wq = on ? sc * (qq < 3 ? muP + muF * Ke * Ke : muO) : 0.0_r;
-            qmMfma(g[0], wq * e0[ks], on ? ej[ks] : 0.0_r, red); qmMfma(g[1], wq * e1[ks], on ? ej[ks] : 0.0_r, red);
+            qmMfma(g[0], wq * e0[ks], on ? ej[ks] : 0.0_r); qmMfma(g[1], wq * e1[ks], on ? ej[ks] : 0.0_r);
           }
         }
         real wb[8];
@@ -703,7 +694,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             pallOpsT(pa, tm);
             // rows 0..15 of Pall^T (columns of Px) have no force-row entries: k steps 0..2 multiply zeros
 #pragma unroll
-            for (int ks = (tm == 0 ? 3 : 0); ks < 8; ++ks) qmMfma(g[tm], pa[ks], wb[ks], red);
+            for (int ks = (tm == 0 ? 3 : 0); ks < 8; ++ks) qmMfma(g[tm], pa[ks], wb[ks]);
           }
         }
         const int j = tn * 16 + l16;

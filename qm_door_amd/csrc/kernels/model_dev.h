@@ -149,18 +149,6 @@ __device__ __forceinline__ void closeSweep2(const ModelR& md, real gravity, cons
   bm.dp = dp; bm.omega = om; bm.com = cm;
 }
 template <class T> using BaseMotion = BaseMotion2<T, T>;
-template <class T>
-__device__ __forceinline__ void closeSweep(const ModelR& md, real gravity, const Accum<T>& acc, const T hn[6], Vec3<T> fsum, Vec3<T> tsum, T sz, T cz, T sy, T cy,
-                                           T f[12], BaseMotion<T>& bm) {
-  Accum2<T, T> a2;
-  a2.M1 = acc.M1; a2.hl = acc.hl; a2.ha = acc.ha; a2.Io = acc.Io;
-  FlowOut<T, T, T> o;
-  closeSweep2<T, T, T>(md, gravity, a2, hn, fsum, tsum, sz, cz, sy, cy, o, bm);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) { f[i] = o.lin[i]; f[3 + i] = o.ang[i]; }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) f[6 + i] = o.kin[i];
-}
 
 // Eigen::Quaternion(Matrix3) (what ocs2::matrixToQuaternion forwards to); q = (x, y, z, w).  Branches on primal values only.
 template <class T> __device__ __forceinline__ void matrixToQuaternion(const Mat3<T>& R, T q[4]) {

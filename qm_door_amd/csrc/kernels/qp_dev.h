@@ -39,7 +39,7 @@ struct QpIo {
   double* Kt;           // [36][ldk] scratch: K tiles, then the rows of L, then the rows of T of the pinned set
   double* wtL;          // [64] scratch: row weights
   double* zs;           // [36] out: solution (lanes >= n write 0)
-  double* red;          // exchange scratch (>= 1024 doubles; the host emulation uses all of it)
+  double* red;          // [512] exchange lines of qpSolve: broadcasts, the small system's right-hand side, column-sum partials, task residual
   double* fork;         // [1] command word of the fork-join with the three helper wavefronts (wbc_kernel): 0 = leave, NP = K tiles of that size
   double* S;            // [QP_KMAX][QP_SLD] scratch: the small system of the pinned rows
   double* Tp;           // [QP_KMAX][ldk] scratch: T_P = L^-1 DZ_P', one row per pinned row (slot order)
@@ -75,7 +75,7 @@ template <int NP, int LDZ_, int LDK_> __device__ __forceinline__ void ipmKTiles(
           av[q] = ja < NP ? w * ra : 0.0; bv[q] = jb < NP ? rb : 0.0;
         }
 #pragma unroll
-        for (int q = 0; q < 7; ++q) qmMfma(acc, av[q], bv[q], io.red);
+        for (int q = 0; q < 7; ++q) qmMfma(acc, av[q], bv[q]);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -120,33 +120,33 @@ template <int LDZ_> __device__ __forceinline__ double ipmColSum(const QpIo& io, 
 // A pivot that does not stand clear of its own rounding -- it is a difference, K_jj - sum_k L_jk^2, rounded relative to K_jj: floorAbs + floorRel (j + 1) K_jj -- marks
 // a direction without curvature: its column of L becomes the unit vector (its row is cleared after the recursion), its right-hand side entry zero (exMask).
 template <int J, int R, int NP> struct IpmDppRows {
-  static __device__ __forceinline__ void run(double* kc, const double* bcP, double ncP, double* red) {
-    if constexpr (R < NP) { qmFmacRowBcast<R % 16, R == J + 3 || R % 16 == 0>(kc[R], bcP[R / 16], ncP, red); IpmDppRows<J, R + 1, NP>::run(kc, bcP, ncP, red); }
+  static __device__ __forceinline__ void run(double* kc, const double* bcP, double ncP) {
+    if constexpr (R < NP) { qmFmacRowBcast<R % 16, R == J + 3 || R % 16 == 0>(kc[R], bcP[R / 16], ncP); IpmDppRows<J, R + 1, NP>::run(kc, bcP, ncP); }
   }
 };
 template <int NP, int J> struct IpmFactorStep {
   static constexpr int NG = (NP + 15) / 16;
-  static __device__ __forceinline__ void run(double* kc, double& myInv, double* bcP, double& ncP, double diag0, double floorAbs, double floorRel, unsigned long long forced, unsigned long long& exMask, int lane, double* red) {
+  static __device__ __forceinline__ void run(double* kc, double& myInv, double* bcP, double& ncP, double diag0, double floorAbs, double floorRel, unsigned long long forced, unsigned long long& exMask, int lane) {
     if constexpr (J < NP) {
-      const double piv = qmReadLane(kc[J], J, red);
-      const double d0 = qmReadLane(diag0, J, red);
+      const double piv = qmReadLane(kc[J], J);
+      const double d0 = qmReadLane(diag0, J);
       const bool ex = ((forced >> J) & 1ull) || !(piv > floorAbs + floorRel * double(J + 1) * d0);     // (wave uniform; NaN pivots count as excluded: the caller checks the result)
       if (ex) exMask |= 1ull << J;
       const double dfl = ex ? 1.0 : piv;
       const double inv = qmRsqrtPos(dfl);
       kc[J] = (lane == J) ? dfl * inv : (ex ? 0.0 : kc[J] * inv);
       if (lane == J) myInv = inv;                              // 1 / L_jj
-      const QmGather gk = qmGather(kc[J], red);                // L[r][j] = gk.get(r)
+      const QmGather gk = qmGather(kc[J]);                // L[r][j] = gk.get(r)
       if constexpr (J + 1 < NP) kc[J + 1] -= gk.get(J + 1) * kc[J];
       if constexpr (J + 2 < NP) kc[J + 2] -= gk.get(J + 2) * kc[J];
-      if constexpr (J >= 1) IpmDppRows<J - 1, J + 2, NP>::run(kc, bcP, ncP, red);     // the previous step's rows J + 2 .. NP - 1
+      if constexpr (J >= 1) IpmDppRows<J - 1, J + 2, NP>::run(kc, bcP, ncP);     // the previous step's rows J + 2 .. NP - 1
       if constexpr (J + 3 < NP) {
-        if constexpr (NG > 0 && (J + 3) / 16 <= 0) bcP[0] = qmReplicateRow<0>(kc[J], red);
-        if constexpr (NG > 1 && (J + 3) / 16 <= 1) bcP[1] = qmReplicateRow<1>(kc[J], red);
-        if constexpr (NG > 2 && (J + 3) / 16 <= 2) bcP[2] = qmReplicateRow<2>(kc[J], red);
+        if constexpr (NG > 0 && (J + 3) / 16 <= 0) bcP[0] = qmReplicateRow<0>(kc[J]);
+        if constexpr (NG > 1 && (J + 3) / 16 <= 1) bcP[1] = qmReplicateRow<1>(kc[J]);
+        if constexpr (NG > 2 && (J + 3) / 16 <= 2) bcP[2] = qmReplicateRow<2>(kc[J]);
         ncP = -kc[J];
       }
-      IpmFactorStep<NP, J + 1>::run(kc, myInv, bcP, ncP, diag0, floorAbs, floorRel, forced, exMask, lane, red);
+      IpmFactorStep<NP, J + 1>::run(kc, myInv, bcP, ncP, diag0, floorAbs, floorRel, forced, exMask, lane);
     }
   }
 };
@@ -175,13 +175,13 @@ __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, i
   QM_DYNAMIC_LDS(ldsBase);
   const QpIo io{ldsBase + off.G, ldsBase + off.AZ, ldsBase + off.rhat, ldsBase + off.DZ, ldsBase + off.fhat, ldsBase + off.Kt, ldsBase + off.wtL, ldsBase + off.zs, ldsBase + off.red, ldsBase + off.fork, ldsBase + off.S, ldsBase + off.Tp};
   enum { ST_I = 0, ST_P = 1, ST_V = 2 };
-  const double* G = io.G; const double* DZ = io.DZ; const double* AZ = io.AZ; double* red = io.red;
+  const double* G = io.G; const double* DZ = io.DZ; const double* AZ = io.AZ;
   double* bc = io.red;              // [0..63] broadcast line (z, multipliers, u, v ...)
   double* ms = io.red + 64;         // [64..127] the small system's right-hand side / solution, by slot
   double* resL = io.red + 384;      // [384..447] task residual, by task row; [448..511] |.| version for the rounding bound
-  auto allSum = [&](double v) { return qmAllSum(v, red); };
-  auto allMax = [&](double v) { return qmAllMax(v, red); };
-  auto allMin = [&](double v) { return qmAllMin(v, red); };
+  auto allSum = [&](double v) { return qmAllSum(v); };
+  auto allMax = [&](double v) { return qmAllMax(v); };
+  auto allMin = [&](double v) { return qmAllMin(v); };
   QM_TICK_DECL;
   const int colL = lane < NP ? lane : 0;       // idle lanes alias column 0 / row 0 (results unused)
   const int rowL = lane < 56 ? lane : 0;
@@ -289,7 +289,7 @@ __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, i
     QM_TICK(10);
     {
       double bcP[3] = {0.0, 0.0, 0.0}, ncP = 0.0;
-      IpmFactorStep<NP, 0>::run(kc, myInv, bcP, ncP, diag0, floorAbs, floorRel, heldMask, exMask, lane, red);
+      IpmFactorStep<NP, 0>::run(kc, myInv, bcP, ncP, diag0, floorAbs, floorRel, heldMask, exMask, lane);
     }
     QM_TICK(11);
     const bool myEx = lane < NP && ((exMask >> lane) & 1ull);
@@ -314,7 +314,7 @@ __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, i
     double tC = 0.0;
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
-      const double tr = qmReadLane(acc * myInv, q, red);
+      const double tr = qmReadLane(acc * myInv, q);
       if (lane == q) tC = tr;
       acc -= (lane > q) ? kc[q] * tr : 0.0;
     }
@@ -324,7 +324,7 @@ __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, i
     double bacc = (lane < NP && ((exMask >> lane) & 1ull)) ? 0.0 : tC, x = 0.0;
 #pragma unroll
     for (int cc = NP - 1; cc >= 0; --cc) {
-      const double dc = qmReadLane(bacc * myInv, cc, red);
+      const double dc = qmReadLane(bacc * myInv, cc);
       if (lane == cc) x = dc;
       bacc -= (lane < cc) ? uc[cc] * dc : 0.0;
     }
@@ -489,7 +489,7 @@ __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, i
 #pragma unroll 1
       while (gm != 0ull) {
         const int b = qmFirstBit(gm); gm &= gm - 1ull;
-        const double kb = qmReadLane(key, b, red);
+        const double kb = qmReadLane(key, b);
         rank += (kb > key || (kb == key && b < lane)) ? 1 : 0;
       }
       if (pinned && guess) slot = qmPopCount(tightMask) + rank;
@@ -586,8 +586,8 @@ __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, i
         }
         for (; q < j; ++q) a0 += Li[q] * Lj[q];
         const double v = Li[j] - (a0 + a1);
-        const double d = qmReadLane(v, j, red);
-        const double sj = qmReadLane(sdiag, j, red);
+        const double d = qmReadLane(v, j);
+        const double sj = qmReadLane(sdiag, j);
         const bool dep = !(d > 1e-11 * sj);
         if (dep) depMask |= 1ull << j;
         const double dj = dep ? 1.0 : sqrt(d);
@@ -659,7 +659,7 @@ __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, i
             for (int u = 0; u < 4; ++u) {
               const int j = j0 + u;
               if (j < k) {
-                const double xj = ((depMask >> j) & 1ull) ? 0.0 : qmReadLane(mval * dinv, j, red);
+                const double xj = ((depMask >> j) & 1ull) ? 0.0 : qmReadLane(mval * dinv, j);
                 mval = (lane == j) ? xj : ((lane > j && lane < k) ? mval - lj[u] * xj : mval);
               }
             }
@@ -673,7 +673,7 @@ __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, i
             for (int u = 0; u < 4; ++u) {
               const int j = j0 - u;
               if (j >= 0) {
-                const double xj = ((depMask >> j) & 1ull) ? 0.0 : qmReadLane(mval * dinv, j, red);
+                const double xj = ((depMask >> j) & 1ull) ? 0.0 : qmReadLane(mval * dinv, j);
                 mval = (lane == j) ? xj : ((lane < j) ? mval - lj[u] * xj : mval);
               }
             }

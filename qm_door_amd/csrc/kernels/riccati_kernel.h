@@ -130,13 +130,13 @@ template <int PF, int NTHR> __device__ __forceinline__ unsigned long long jointR
 // state and the multiply-add -- applied one step late so that the replication's round trip through the LDS crossbar is off the chain;
 // rows 16, 17 (m~ > 16) by v_readlane.  Row updates of one row commute, so the order does not matter.
 template <int J, int R, int REND> struct RiccatiDppRows {
-  static __device__ __forceinline__ void run(real* col, real bc, real nc, real* scr) {
-    if constexpr (R < REND) { qmFmacRowBcast<R, R == J + 3>(col[R], bc, nc, scr); RiccatiDppRows<J, R + 1, REND>::run(col, bc, nc, scr); }
+  static __device__ __forceinline__ void run(real* col, real bc, real nc) {
+    if constexpr (R < REND) { qmFmacRowBcast<R, R == J + 3>(col[R], bc, nc); RiccatiDppRows<J, R + 1, REND>::run(col, bc, nc); }
   }
 };
 template <int NT, int J> struct RiccatiStep {
   static constexpr int DEND = NT < 16 ? NT : 16;    // DPP rows end here
-  static __device__ __forceinline__ void run(real* col, real& inv, real& bcP, real& ncP, int& status, real* scr, real* out, int ostr) {
+  static __device__ __forceinline__ void run(real* col, real& inv, real& bcP, real& ncP, int& status, real* out, int ostr) {
     if constexpr (J < NT) {
       col[J] *= inv;                                     // row J of [L^T | W] / sqrt(pivot)
       // final: element (c, J) of L for an H lane, (J, c) of W for a G lane (asynchronous LDS write); lane J's own entry is L_JJ.  (Until round 6 every lane
@@ -145,25 +145,25 @@ template <int NT, int J> struct RiccatiStep {
       // diagonal is inverted after the factorisation now, while this wavefront has nothing to do: riccatiInvertDiagonal.)
       *out = col[J];
       out += ostr;
-      const QmGather gj = qmGather(col[J], scr);
+      const QmGather gj = qmGather(col[J]);
       if constexpr (J + 1 < NT) {
         col[J + 1] -= gj.get(J + 1) * col[J];
-        const real piv = qmReadLane(col[J + 1], J + 1, scr);
+        const real piv = qmReadLane(col[J + 1], J + 1);
         if (!(piv > REAL_PIVOT_MIN)) status = 1;         // beside the chain: a failed pivot (not a positive number) flags the instance, whose step is then discarded (linesearch_kernel) ...
         inv = qmRsqrtPos(fmax(piv, REAL_PIVOT_MIN));     // ... and the factorisation runs on with the pivot floored: ONE instruction on the chain (fmax drops a NaN) where the exact
                                                          // select "failed ? 1 : piv" was a compare, two scalar selects and their way back to the vector unit.  Started here: its latency hides behind the remaining updates
       }
       if constexpr (J + 2 < NT) col[J + 2] -= gj.get(J + 2) * col[J];
-      if constexpr (J >= 1) RiccatiDppRows<J - 1, J + 2, DEND>::run(col, bcP, ncP, scr);     // the previous step's rows J + 2 .. 15
+      if constexpr (J >= 1) RiccatiDppRows<J - 1, J + 2, DEND>::run(col, bcP, ncP);     // the previous step's rows J + 2 .. 15
 #pragma unroll
       for (int r = (J + 3 > 16 ? J + 3 : 16); r < NT; ++r) col[r] -= gj.get(r) * col[J];
-      if constexpr (J + 3 < DEND) { bcP = qmReplicateRow0(col[J], scr); ncP = -col[J]; }
-      RiccatiStep<NT, J + 1>::run(col, inv, bcP, ncP, status, scr, out, ostr);
+      if constexpr (J + 3 < DEND) { bcP = qmReplicateRow0(col[J]); ncP = -col[J]; }
+      RiccatiStep<NT, J + 1>::run(col, inv, bcP, ncP, status, out, ostr);
     }
   }
 };
 
-template <int NT> __device__ __forceinline__ void riccatiFactorise(const real* T, real* W, real* LL, int nt, int lane, int& status, real* scr, unsigned long long* tk = nullptr) {
+template <int NT> __device__ __forceinline__ void riccatiFactorise(const real* T, real* W, real* LL, int nt, int lane, int& status, unsigned long long* tk = nullptr) {
   const bool isH = lane < MT, isG = lane >= MT && lane < MT + 31;
   const int c = isH ? lane : (isG ? lane - MT : 0);
 #ifdef QM_RICCATI_TIMING
@@ -186,7 +186,7 @@ template <int NT> __device__ __forceinline__ void riccatiFactorise(const real* T
   // steps j >= nt meet identity columns (pivot 1, multipliers 0): no branch, one basic block
   real inv, bcP = 0.0_r, ncP = 0.0_r;
   {
-    const real piv = qmReadLane(col[0], 0, scr);
+    const real piv = qmReadLane(col[0], 0);
     if (!(piv > REAL_PIVOT_MIN)) status = 1;
     inv = qmRsqrtPos(fmax(piv, REAL_PIVOT_MIN));
   }
@@ -194,7 +194,7 @@ template <int NT> __device__ __forceinline__ void riccatiFactorise(const real* T
   // elimination residue and never read), G lane c column c of W, the idle lanes a scratch word (row 19 of L)
   real* out = isH ? LL + c * LDS_LL : (isG ? W + c : LL + 19 * LDS_LL);
   const int ostr = isH ? 1 : (isG ? LDS_W : 0);
-  RiccatiStep<NT, 0>::run(col, inv, bcP, ncP, status, scr, out, ostr);
+  RiccatiStep<NT, 0>::run(col, inv, bcP, ncP, status, out, ostr);
 #ifdef QM_RICCATI_TIMING
   { real keep_ = col[NT - 1]; QM_KEEP(keep_); col[NT - 1] = keep_; }
   const unsigned long long tq1 = clock64();
@@ -302,7 +302,7 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
   if (a.done[inst]) return;   // workgroup uniform
   const int N = a.N;
   real* S = lds + R_S; real* Y = lds + R_Y; real* T = lds + R_T;
-  real* scr = nullptr; real* red = lds + R_SCR;
+  real* red = lds + R_SCR;
   const real* stagesI = a.stages + size_t(inst) * (N + 1) * STAGE_DOUBLES;
   const real* gainsI = a.gains + size_t(inst) * N * GAIN_DOUBLES;
   const int* ncI = a.stageNc + size_t(inst) * (N + 1);
@@ -444,7 +444,7 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
         c[r] = i < 30 ? v : 0.0_r;
       }
 #pragma unroll
-      for (int ks = 0; ks < 8; ++ks) qmMfma(c, av[ks], bw[ks], scr);
+      for (int ks = 0; ks < 8; ++ks) qmMfma(c, av[ks], bw[ks]);
       return c;
     };
     // The off-diagonal tile (0,1) belongs to wavefront 2, which also forms the gains of the previous stage -- with both it was the longest wavefront of the
@@ -467,12 +467,12 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
       bv[7] = bv[7] * m7One + mAdd7;
       if (splitK) {
 #pragma unroll
-        for (int ks = 0; ks < KS3; ++ks) { qmMfma(c0, a0[ks], bv[ks], scr); qmMfma(c1, a1[ks], bv[ks], scr); }
+        for (int ks = 0; ks < KS3; ++ks) { qmMfma(c0, a0[ks], bv[ks]); qmMfma(c1, a1[ks], bv[ks]); }
 #pragma unroll
-        for (int ks = KS3; ks < 8; ++ks) qmMfma(c0, a0[ks], bv[ks], scr);
+        for (int ks = KS3; ks < 8; ++ks) qmMfma(c0, a0[ks], bv[ks]);
       } else {
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) { qmMfma(c0, a0[ks], bv[ks], scr); qmMfma(c1, a1[ks], bv[ks], scr); }
+        for (int ks = 0; ks < 8; ++ks) { qmMfma(c0, a0[ks], bv[ks]); qmMfma(c1, a1[ks], bv[ks]); }
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) { Y[(h + 4 * r) * LDS_Y + jc] = c0[r]; Y[(16 + h + 4 * r) * LDS_Y + jc] = c1[r]; }
@@ -498,7 +498,7 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
 #pragma unroll
-        for (int t = 0; t < 3; ++t) qmMfma(d[t], a1[q], bt[t][q], scr);
+        for (int t = 0; t < 3; ++t) qmMfma(d[t], a1[q], bt[t][q]);
       }
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
@@ -534,12 +534,12 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
 #pragma unroll
         for (int r = 0; r < 4; ++r) c1[r] = ci[4 + r] * cOne;
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) { qmMfma(c0, a0[ks], bv[ks], scr); qmMfma(c1, a1[ks], bv[ks], scr); }
+        for (int ks = 0; ks < 8; ++ks) { qmMfma(c0, a0[ks], bv[ks]); qmMfma(c1, a1[ks], bv[ks]); }
 #pragma unroll
         for (int r = 0; r < 4; ++r) { T[(h + 4 * r) * LDS_Y + jc] = c0[r]; T[(16 + h + 4 * r) * LDS_Y + jc] = c1[r]; }
       } else {
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) qmMfma(c0, a0[ks], bv[ks], scr);
+        for (int ks = 0; ks < 8; ++ks) qmMfma(c0, a0[ks], bv[ks]);
 #pragma unroll
         for (int r = 0; r < 4; ++r) T[(h + 4 * r) * LDS_Y + jc] = c0[r];
       }
@@ -563,10 +563,10 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
       // the elimination is unrolled for the stage's number of projected inputs: 18 stance, 17 three-leg support, 16 trot, 14 flight
       __builtin_amdgcn_s_setprio(3);    // the wavefront on the critical path of the stage goes first at the shared units (LDS)
       switch (nt) {
-        case 16: riccatiFactorise<16>(T, W, LL, nt, lane, status, scr QM_TK); break;
-        case 14: riccatiFactorise<14>(T, W, LL, nt, lane, status, scr QM_TK); break;
-        case 17: riccatiFactorise<17>(T, W, LL, nt, lane, status, scr QM_TK); break;
-        default: riccatiFactorise<MT>(T, W, LL, nt, lane, status, scr QM_TK); break;
+        case 16: riccatiFactorise<16>(T, W, LL, nt, lane, status QM_TK); break;
+        case 14: riccatiFactorise<14>(T, W, LL, nt, lane, status QM_TK); break;
+        case 17: riccatiFactorise<17>(T, W, LL, nt, lane, status QM_TK); break;
+        default: riccatiFactorise<MT>(T, W, LL, nt, lane, status QM_TK); break;
       }
       __builtin_amdgcn_s_setprio(0);
     } else {
@@ -621,7 +621,7 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
 #pragma unroll
       for (int ks = 0; ks < 5; ++ks) { const int kk = 4 * ks + h; av[ks] = -W[kk * LDS_W + tm * 16 + la]; bw[ks] = W[kk * LDS_W + j]; }
 #pragma unroll
-      for (int ks = 0; ks < 5; ++ks) qmMfma(c6, av[ks], bw[ks], scr);
+      for (int ks = 0; ks < 5; ++ks) qmMfma(c6, av[ks], bw[ks]);
       // one store per accumulator register, no branch: an entry of the padding (row / column 30, 31: they must stay zero) goes to a scratch word of the
       // symmetrisation square (free here), the s' entry (column 30) to row 30 of S; the mirror image of the off-diagonal tile likewise
       real* sink = lds + R_SYM + lane;

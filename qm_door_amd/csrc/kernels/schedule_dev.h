@@ -16,13 +16,6 @@ struct Schedule {
   const int* modes;          // [MAX_EVENTS+1]
 };
 
-// Continuous-time lookup (policy evaluation): std::lower_bound on the event times (upstream ModeSchedule::modeAtTime ->
-// lookup::findIndexInTimeArray): an event time itself still belongs to the phase before it.
-__device__ __forceinline__ int phaseAt(const Schedule& s, real t) {
-  int i = 0;
-  while (i < s.numEvents && s.eventTimes[i] < t) ++i;
-  return i;
-}
 // Mode lookup of a SHOOTING NODE: a node placed exactly on an event time is upstream's PostEvent node (evaluated at
 // t + weakEpsilon by ocs2_sqp's getIntervalStart), so it takes the mode that STARTS there: std::upper_bound.
 __device__ __forceinline__ int nodePhaseAt(const Schedule& s, real t) {

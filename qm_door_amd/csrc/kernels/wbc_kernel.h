@@ -58,8 +58,8 @@ constexpr int W_DZ = W_AZ + MAXR * LDZ;          // D0 Z [MAXM][LDZ]
 constexpr int W_K = W_DZ + MAXM * LDZ;           // K / Cholesky [36][LDK]
 constexpr int W_G = W_K + ND * LDK;              // G = AZ^T AZ + eps [36][LDK]
 constexpr int W_VH = W_G + ND * LDK;             // Householder vectors [MAXR][40]
-constexpr int W_VEC = W_VH + MAXR * 40;          // vectors: x[36] z[36] g[36] rd[36] rhs[36] dz[36] fhat[56] lam[56] wt[56] tz[56] red[64]
-constexpr int W_BODY2 = W_VEC + 6 * 36 + 4 * 56 + 1024 + 8;   // (red[1024]: wavefront exchange scratch, only the host emulation uses more than 64) body / dof tables of the desired pass (wavefront 1)
+constexpr int W_VEC = W_VH + MAXR * 40;          // vectors: x[36] z[36] g[36] rd[36] rhs[36] dz[36] fhat[56] lam[56] wt[56] tz[56] red[1024]
+constexpr int W_BODY2 = W_VEC + 6 * 36 + 4 * 56 + 1024 + 8;   // (red[1024]: the level solver's exchange lines red[0..511] (qp_dev.h: qpSolve), the fork-join's job red[512..521]) body / dof tables of the desired pass (wavefront 1)
 constexpr int W_DOF2 = W_BODY2 + 640;
 constexpr int W_TP = W_DOF2 + 144;               // T_P = L^-1 DZ_P' of the level solver's pinned rows [QP_KMAX][LDK] (round 6; until then over the K square, one row at a time)
 constexpr int WBC_LDS_DOUBLES = W_TP + QP_KMAX * LDK;
@@ -178,28 +178,6 @@ __device__ __forceinline__ void symMul(const double* I6, const double* v, double
   o[0] = I6[0] * v[0] + I6[1] * v[1] + I6[2] * v[2]; o[1] = I6[1] * v[0] + I6[3] * v[1] + I6[4] * v[2]; o[2] = I6[2] * v[0] + I6[4] * v[1] + I6[5] * v[2];
 }
 
-__device__ __forceinline__ double wbcSum(double* red, int lane, double v) { red[lane] = v; QM_WAVE_SYNC(); double s = 0; for (int i = 0; i < 64; ++i) s += red[i]; QM_WAVE_SYNC(); return s; }
-__device__ __forceinline__ double wbcMax(double* red, int lane, double v) { red[lane] = v; QM_WAVE_SYNC(); double s = red[0]; for (int i = 1; i < 64; ++i) s = fmax(s, red[i]); QM_WAVE_SYNC(); return s; }
-__device__ __forceinline__ double wbcMin(double* red, int lane, double v) { red[lane] = v; QM_WAVE_SYNC(); double s = red[0]; for (int i = 1; i < 64; ++i) s = fmin(s, red[i]); QM_WAVE_SYNC(); return s; }
-
-// In-place Cholesky of the n x n matrix K (row stride LDK) in LDS, lane = row; pivots are floored at floorv
-// (1e-13 x the largest diagonal entry of the level's cost Hessian G, as in the oracle's choleskyFloored).
-__device__ inline void ldsCholesky(double* K, int n, int lane, double floorv) {
-#pragma unroll 1
-  for (int j = 0; j < n; ++j) {
-    const double d = K[j * LDK + j];
-    const double dj = sqrt(d > floorv ? d : floorv);
-    QM_WAVE_SYNC();
-    if (lane == j) K[j * LDK + j] = dj;
-    else if (lane > j && lane < n) K[lane * LDK + j] = K[lane * LDK + j] / dj;
-    QM_WAVE_SYNC();
-    if (lane > j && lane < n) {
-      const double lij = K[lane * LDK + j];
-      for (int q = j + 1; q <= lane; ++q) K[lane * LDK + q] -= lij * K[q * LDK + j];
-    }
-    QM_WAVE_SYNC();
-  }
-}
 // Solve L L^T x = y in place (y in LDS), lane = row.
 __device__ inline void ldsCholSolve(const double* L, int n, double* y, int lane) {
 #pragma unroll 1
@@ -226,11 +204,10 @@ __device__ inline void ldsCholSolve(const double* L, int n, double* y, int lane)
 // unit rows: exact ties are the rule, and the basis -- the coordinates the minimum-norm representative of a level is taken in -- depends on the order.  The kernels and the
 // CPU restatement of the tests take the same decisions with the same roundings.  Result: N (n x nNew, row stride LDK) in K; returns nNew.
 // Also used for the implied equalities of a level (rows = the strongly active inequality rows, wbc_kernel).  A called function: three call sites, one copy; the arrays
-// arrive as offsets into the dynamic LDS (qp_dev.h: qpSolve).
+// arrive as offsets into the dynamic LDS (qp_dev.h: qpSolve).  redOff is not read: it stays in the signature because dropping it changes how wbc_kernel is compiled.
 __device__ __attribute__((noinline)) int wbcNullSpace(int rowsOff, int r, int n, int kOff, int vhOff, int redOff, int lane) {
   QM_DYNAMIC_LDS(ldsBase);
-  double* rows = ldsBase + rowsOff; double* K = ldsBase + kOff; double* Vh = ldsBase + vhOff; double* red = ldsBase + redOff;
-  (void)red;
+  double* rows = ldsBase + rowsOff; double* K = ldsBase + kOff; double* Vh = ldsBase + vhOff;
   QM_TICK_DECL;
   static_assert(MAXR <= 24 && ND <= 36 && 128 + 64 + 32 <= MAXR * 40, "index tables of the null-space step fit the region they are carved from");
   {
@@ -271,13 +248,13 @@ __device__ __attribute__((noinline)) int wbcNullSpace(int rowsOff, int r, int n,
 #pragma unroll 1
       for (int k = 0; k < size; ++k) {
         const bool mine = lane < r && rowPos >= k;
-        const double gmax = qmAllMax(mine ? best : -1.0, red);
+        const double gmax = qmAllMax(mine ? best : -1.0);
         if (!(gmax > 0.0)) break;
         const bool cand = mine && best == gmax;
         const unsigned long long tied = qmBallot(cand);
         int Lp;
         if ((tied & (tied - 1)) == 0) Lp = qmFirstBit(tied);
-        else Lp = int(qmAllMin(cand ? double((bj * 64 + rowPos) * 64 + lane) : 1e9, red)) & 63;   // ties between rows: the smallest COLUMN position, then the smallest row position (Eigen's column-major scan)
+        else Lp = int(qmAllMin(cand ? double((bj * 64 + rowPos) * 64 + lane) : 1e9)) & 63;   // ties between rows: the smallest COLUMN position, then the smallest row position (Eigen's column-major scan)
         const int pr = qmReadLaneInt(rowPos, Lp), pc = qmReadLaneInt(bj, Lp);
         QM_TICK(1);
         maxPivot = fmax(maxPivot, gmax);
@@ -411,8 +388,8 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
   double* fhat = carve + (W_VEC + 6 * 36); double* lam = fhat + 56; double* wt = lam + 56; double* tzv = wt + 56; double* red = carve + (W_VEC + 6 * 36 + 4 * 56); double* ctl = red + 1024;
 
   // Wavefront 0 solves the instance; the other three sit on the CU's idle SIMDs and take their share of the matrix-core tiles of the
-  // interior point between two workgroup barriers (ipm_dev.h: ipmKTiles).  Command word: ctl[4] (0 = leave).
-  double* forkCmd = ctl + 4; double* forkJob = red + 512;   // (red[0..63] carries the interior point's broadcasts, red[128..383] its partial sums; nothing else of it is used on the GPU)
+  // interior point between two workgroup barriers (qp_dev.h: ipmKTiles).  Command word: ctl[4] (0 = leave).
+  double* forkCmd = ctl + 4; double* forkJob = red + 512;   // (behind the level solver's red[0..511]: qp_dev.h, qpSolve)
   // ---- S5: desired pass (WbcBase.cpp:205-237), on wavefront 1 while wavefront 0 runs the measured pass, M, nle and the Jacobians: it has its own
   //      body / dof tables and writes only v_des of the base and the desired entries of mi, none of which is read before the join after S4.
   //      v_des base from the centroidal map (WbcBase.cpp:217-219) with the MPC's own sweep.
@@ -497,8 +474,8 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
       else {   // 100 / 101: C = A B / A^T B, described in forkJob (pointers as offsets from the LDS base)
         const double* jA = lds + int(forkJob[0]); const double* jB = lds + int(forkJob[2]); double* jD = lds + int(forkJob[7]);
         const int lda = int(forkJob[1]), ldb = int(forkJob[3]), jM = int(forkJob[4]), jN = int(forkJob[5]), jK = int(forkJob[6]), ldd = int(forkJob[8]);
-        if (op == 101) waveGemmTiles<true>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, forkJob[9], wave, lane, red);
-        else waveGemmTiles<false>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, forkJob[9], wave, lane, red);
+        if (op == 101) waveGemmTiles<true>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, forkJob[9], wave, lane);
+        else waveGemmTiles<false>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, forkJob[9], wave, lane);
       }
       QM_LDS_BARRIER();
     }
@@ -511,8 +488,8 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
       forkJob[7] = double(jD - lds); forkJob[8] = ldd; forkJob[9] = diagAdd; forkCmd[0] = ta ? 101.0 : 100.0;
     }
     QM_LDS_BARRIER();
-    if (ta) waveGemmTiles<true>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, diagAdd, 0, lane, red);
-    else waveGemmTiles<false>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, diagAdd, 0, lane, red);
+    if (ta) waveGemmTiles<true>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, diagAdd, 0, lane);
+    else waveGemmTiles<false>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, diagAdd, 0, lane);
     QM_LDS_BARRIER();
   };
   const int mode = a.mode[inst];
@@ -747,7 +724,7 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
       QM_WAVE_SYNC();
       forkGemm(false, AZp, LDZ, Zn, LDZ, rRows, rRows, nQ, K, LDK, 0.0);
       QM_WAVE_SYNC();
-      const double dmax = qmAllMax(lane < rRows ? K[lane * LDK + lane] : 0.0, red);
+      const double dmax = qmAllMax(lane < rRows ? K[lane * LDK + lane] : 0.0);
       // plain Cholesky in LDS (lane = row); a pivot lost against the diagonal (dependent task rows) ends the attempt
       bool ok = true;
 #pragma unroll 1
@@ -778,9 +755,9 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
         double res = 0.0, rsc = 1.0, dzr = 0.0;
         if (lane < rRows) { res = rhatp[lane]; for (int c = 0; c < nQ; ++c) res += AZp[lane * LDZ + c] * zs[c]; rsc = fabs(rhatp[lane]); }
         if (lane < m0) { for (int c = 0; c < nQ; ++c) dzr += DZ[lane * LDZ + c] * zs[c]; dzr -= fhat[lane]; }
-        const double resmax = qmAllMax(fabs(res), red), rscale = fmax(1.0, qmAllMax(rsc, red));
+        const double resmax = qmAllMax(fabs(res)), rscale = fmax(1.0, qmAllMax(rsc));
         const bool viol = rowOn && !(dzr <= 0.0);
-        const double nanProbe = qmAllSum(zc, red);
+        const double nanProbe = qmAllSum(zc);
         ok = resmax <= 1e-9 * rscale && qmBallot(viol) == 0ull && nanProbe == nanProbe;
       }
       if (ok) { passes = 0; strongOut = false; return 0; }

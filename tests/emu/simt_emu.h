@@ -38,10 +38,7 @@ inline void __builtin_amdgcn_s_setprio(int) {}
 #define QM_TICK(slot)
 #define QM_TICK_FLUSH(base, cond)
 #define QM_STREAM_STORE(ptr, value) (*(ptr) = (value))
-#define QM_STREAM_LOAD(ptr) (*(ptr))
-#define QM_L2_LOAD(ptr) (*(ptr))
 #define QM_CONSTANT_REF(T, lvalue) (lvalue)
-#define QM_CONSTANT_PTR(T, ptr) (ptr)
 #define QM_SCHED_FENCE()
 #define QM_LDS_BARRIER() __syncthreads()
 #define __device__
@@ -61,53 +58,54 @@ using std::max; using std::min;
 
 // ---- wavefront exchange primitives.  The lanes of a wavefront exchange values through a buffer the EMULATION owns (one per
 // wavefront of the running workgroup: two 128-double halves used alternately, so one barrier per exchange suffices -- a lane can
-// only be one exchange ahead of the slowest lane of its wavefront).  The `scratch` argument of the primitives is ignored: product
-// kernels need no LDS for these operations (they are register / DPP / v_readlane instructions on the GPU).
+// only be one exchange ahead of the slowest lane of its wavefront).  Product kernels need no LDS for these operations (they are
+// register / DPP / v_readlane instructions on the GPU).
 inline thread_local unsigned g_emuXchg = 0;
-constexpr int kEmuWaveScratch = 4096;
+constexpr int kEmuWaveScratch = 2 * 128;
 inline std::vector<std::unique_ptr<double[]>> g_emuWaveScratch;
-inline double* emuWaveScratch() { return g_emuWaveScratch[(threadIdx.x + blockDim.x * (threadIdx.y + blockDim.y * threadIdx.z)) / 64].get(); }
-inline double* emuXchgBuf(double*) { return emuWaveScratch() + 128 * ((g_emuXchg++) & 1u); }
+inline double* emuXchgBuf() {
+  return g_emuWaveScratch[(threadIdx.x + blockDim.x * (threadIdx.y + blockDim.y * threadIdx.z)) / 64].get() + 128 * ((g_emuXchg++) & 1u);
+}
 
 // The primitives are templates over the arithmetic type T (double for the fp64 build, float for the fp32 build of the MPC kernels); the
 // exchange buffers hold doubles either way (every float is exactly representable).
-template <class T> inline T qmShflXor(T v, int mask, T* scratch = nullptr) {
+template <class T> inline T qmShflXor(T v, int mask) {
   const unsigned lane = threadIdx.x & 63u;
-  double* buf = emuXchgBuf(nullptr); (void)scratch;
+  double* buf = emuXchgBuf();
   buf[lane] = double(v);
   QM_WAVE_SYNC();
   return T(buf[lane ^ unsigned(mask)]);
 }
 
-template <int R, bool FIRST, class T> inline void qmFmacRowBcast(T& acc, T bc, T m, T* = nullptr) {   // v_fmac_*_dpp row_newbcast:R
+template <int R, bool FIRST, class T> inline void qmFmacRowBcast(T& acc, T bc, T m) {   // v_fmac_*_dpp row_newbcast:R
   const unsigned lane = threadIdx.x & 63u;
-  double* buf = emuXchgBuf(nullptr);
+  double* buf = emuXchgBuf();
   buf[lane] = double(bc);
   QM_WAVE_SYNC();
   acc += T(buf[(lane & ~15u) + unsigned(R)]) * m;
 }
-template <int G, class T> inline T qmReplicateRow(T v, T* = nullptr) {   // ds_bpermute with address 16 G + (lane & 15)
+template <int G, class T> inline T qmReplicateRow(T v) {   // ds_bpermute with address 16 G + (lane & 15)
   const unsigned lane = threadIdx.x & 63u;
-  double* buf = emuXchgBuf(nullptr);
+  double* buf = emuXchgBuf();
   buf[lane] = double(v);
   QM_WAVE_SYNC();
   return T(buf[16u * unsigned(G) + (lane & 15u)]);
 }
-template <class T> inline T qmReplicateRow0(T v, T* s = nullptr) { return qmReplicateRow<0>(v, s); }
+template <class T> inline T qmReplicateRow0(T v) { return qmReplicateRow<0>(v); }
 template <class T> inline T qmHalfXor32(T v, bool) { return qmShflXor(v, 32); }   // v_permlane32_swap
 inline int qmReadLaneInt(int v, int src);
 template <class T> inline T qmRowXor16(T v, bool) { return qmShflXor(v, 16); }    // v_permlane16_swap
 
-template <class T> inline T qmReadLane(T v, int src, T* scratch = nullptr) {
+template <class T> inline T qmReadLane(T v, int src) {
   const unsigned lane = threadIdx.x & 63u;
-  double* buf = emuXchgBuf(nullptr); (void)scratch;
+  double* buf = emuXchgBuf();
   buf[lane] = double(v);
   QM_WAVE_SYNC();
   return T(buf[unsigned(src) & 63u]);
 }
 inline int qmReadLaneInt(int v, int src) { return qmReadLane<int>(v, src); }
 inline unsigned long long qmBallot(bool p) {
-  double* buf = emuXchgBuf(nullptr);
+  double* buf = emuXchgBuf();
   buf[threadIdx.x & 63u] = p ? 1.0 : 0.0;
   QM_WAVE_SYNC();
   unsigned long long m = 0;
@@ -121,9 +119,9 @@ template <class T> struct QmGatherT {
   T vals[64];
   T get(int src) const { return vals[src & 63]; }
 };
-template <class T> inline QmGatherT<T> qmGather(T v, T* scratch = nullptr) {
+template <class T> inline QmGatherT<T> qmGather(T v) {
   const unsigned lane = threadIdx.x & 63u;
-  double* buf = emuXchgBuf(nullptr); (void)scratch;
+  double* buf = emuXchgBuf();
   buf[lane] = double(v);
   QM_WAVE_SYNC();
   QmGatherT<T> g;
@@ -139,9 +137,9 @@ template <class T, class Op> inline T emuButterfly(T v, Op op) {
     for (int i = 0; i < 64; ++i) cur[i] = nxt[i]; }
   return cur[lane];
 }
-template <class T> inline T qmAllSum(T v, T* = nullptr) { return emuButterfly(v, [](T a, T b) { return a + b; }); }
-template <class T> inline T qmAllMax(T v, T* = nullptr) { return emuButterfly(v, [](T a, T b) { return std::fmax(a, b); }); }
-template <class T> inline T qmAllMin(T v, T* = nullptr) { return emuButterfly(v, [](T a, T b) { return std::fmin(a, b); }); }
+template <class T> inline T qmAllSum(T v) { return emuButterfly(v, [](T a, T b) { return a + b; }); }
+template <class T> inline T qmAllMax(T v) { return emuButterfly(v, [](T a, T b) { return std::fmax(a, b); }); }
+template <class T> inline T qmAllMin(T v) { return emuButterfly(v, [](T a, T b) { return std::fmin(a, b); }); }
 
 // 16x16x4 matrix-core instruction on host threads: lane l supplies a = A[l % 16][l / 16], b = B[l / 16][l % 16]; the accumulator maps of the
 // HARDWARE are emulated (measured on gfx950, tools/probe_mfma.hip; cdna4 ISA): register r of lane l is C[l / 16 + 4 r][l % 16] for fp64 and
@@ -157,27 +155,14 @@ template <class T> inline void emuMfmaTile(QmAccT<T>& c, const double* A, const 
     c.v[r] = acc;
   }
 }
-template <class T> inline void qmMfma(QmAccT<T>& c, T a, T b, T* scratch = nullptr) {
+template <class T> inline void qmMfma(QmAccT<T>& c, T a, T b) {
   const unsigned lane = threadIdx.x & 63u;
-  double* buf = emuXchgBuf(nullptr); (void)scratch;
+  double* buf = emuXchgBuf();
   buf[lane] = double(a); buf[64 + lane] = double(b);
   QM_WAVE_SYNC();
   emuMfmaTile(c, buf, buf + 64, lane);
 }
-// all upper-triangle tiles of one k step with a single exchange (own region behind the 256 doubles of the plain exchanges)
-template <int TP, class T> inline void qmMfmaUpper(QmAccT<T>* acc, const T* a, const T* b, T* scratch = nullptr) {
-  const unsigned lane = threadIdx.x & 63u;
-  (void)scratch;
-  double* buf = emuWaveScratch() + 256 + (TP * 128) * ((g_emuXchg++) & 1u);
-  for (int t = 0; t < TP; ++t) { buf[t * 128 + lane] = double(a[t]); buf[t * 128 + 64 + lane] = double(b[t]); }
-  QM_WAVE_SYNC();
-  int t = 0;
-  for (int ti = 0; ti < TP; ++ti)
-    for (int tj = ti; tj < TP; ++tj, ++t) emuMfmaTile(acc[t], buf + ti * 128, buf + tj * 128 + 64, lane);
-}
 inline double __longlong_as_double(long long v) { double d; std::memcpy(&d, &v, 8); return d; }
-inline double qmRsqrt(double x) { return 1.0 / std::sqrt(x); }
-inline float qmRsqrt(float x) { return 1.0f / std::sqrt(x); }
 inline double qmRsqrtPos(double x) { return 1.0 / std::sqrt(x); }
 inline double qmMulNoFma(double a, double b) { volatile double p = a * b; return p; }
 inline double qmSubNoFma(double a, double b) { volatile double d = a - b; return d; }
@@ -186,7 +171,6 @@ inline double qmRcpPos(double x) { return 1.0 / x; }
 inline float qmRcpPos(float x) { return 1.0f / x; }
 #define QM_KEEP(x) (void)(x)
 #define QM_OPAQUE_LDS(T, name, p) T* name = (p)
-#define QM_LDS_CONST_PTR(T) const T*
 #define QM_TO_LDS_PTR(T, p) ((const T*)(p))
 namespace qmk {
 using QmAcc = QmAccT<real>;

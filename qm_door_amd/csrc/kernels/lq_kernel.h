@@ -1,7 +1,7 @@
 // lq_node_kernel -- per-node cost, constraint projection and projected stage record.  One wavefront per shooting node.
 // The derivative rows it consumes come from ad_node_kernel (ad_kernel.h): two launches so that each half gets the occupancy it can
-// use -- the AD sweep is fp64-VALU bound and needs the whole register file, the projection is latency bound and runs two wavefronts
-// per SIMD (19.7 KiB of LDS, 187 VGPRs).  The AD rows (17 KiB per node) cross HBM once in between.
+// use -- the AD sweep is fp64-VALU bound and needs the whole register file, the projection is latency bound and runs three wavefronts
+// per SIMD (12.7 KiB of LDS, 168 VGPRs).  The AD rows (17 KiB per node) cross HBM once in between.
 //
 // Replaces, per node: the quadratic approximation of the tracking cost / EE soft
 // constraint / joint-limit and friction-cone barriers (QMInterface.cpp:99-121) and upstream ocs2_sqp's QR constraint projection.
@@ -14,29 +14,41 @@
 
 namespace qmk {
 
-// LDS of lq_node_kernel (doubles): 19.7 KiB per node, eight nodes per CU = TWO wavefronts per SIMD.  The kernel is latency bound
-// (readlane chains, LDS round trips, dependent matrix-core accumulations): at one wavefront per SIMD it ran 1.10 ms per launch.
-// What keeps it this small:
+// LDS of lq_node_kernel (doubles): 12.7 KiB per node, twelve nodes per CU = THREE wavefronts per SIMD.  The kernel is latency bound
+// (readlane chains, LDS round trips, dependent matrix-core accumulations): at one wavefront per SIMD it ran 1.10 ms per launch, at
+// two 0.44 ms, at three 0.39 ms.  What keeps it this small:
 //   * Pall = [Px | Pe | 0 | Pu] is stored for its 18 dense joint-velocity rows only; the 12 force rows are unit vectors / pinned
 //     values and are synthesised into the matrix-core operands from registers;
 //   * R' and Q never enter LDS: the operand / accumulator entries are assembled where they are needed from the constant
 //     matrices (global, L1 resident) plus the few barrier terms parked in LDS;
-//   * W = R Pall is produced and consumed one 16-column tile at a time;
-//   * region X is recycled four times.
+//   * the dense rows of [A | B] never enter LDS: products (1) reads its operands straight from the AD rows (global, cache resident);
+//   * W = R Pall is produced one 16-column tile at a time and never enters LDS: in the fp64 accumulator map register r of a lane
+//     holds row h + 4 r, which is the row of k step r it supplies as a B operand (gpu_rt.h; the fp32 build permutes A rows to the
+//     same map), so the tile feeds G = Pall^T W from the registers it was accumulated in;
+//   * the zero rows of Q_v (18..31) and of Y (12..15) are synthesised into the operands, not stored.
+// Regions and live ranges (QM_TICK sections; every hand-off between aliases crosses a QM_WAVE_SYNC()):
+//   X   x u x_next dx [4][32]      ticks 0..3  (dead at the sync in front of the QR, tick 5)
+//       Q_v [18][LDQ]              tick 5 (published after the QR) .. the sync after Pall is complete (tick 6)
+//       fin[64], red[64]           at X + 128, X + 192: red in the terminal path (tick 1) and after products (1); fin in products
+//                                  (2)(3) -- neither meets Q_v, and neither overlaps x u x_next dx
+//   PA  [C | D_v] [16][CDW]        ticks 0..5 (dead at the sync in front of the QR)
+//       Y [12][LDY]                tick 5: published after the QR, read by -Q_v1 Y (dead at the sync in front of the Pall stores)
+//       Pall rows 12..29 [18][PAW] tick 5 .. the end of products (2)(3)
+//   EEJ [6][32]                    ticks 0..9
+//   VEC b r e eeh pe fb ddp ddv q cost  ticks 0..9
 constexpr int PAW = 50;                      // row stride of the dense rows of Pall (columns 0..29 Px, 30 Pe, 31 zero, 32..32+m~-1 Pu)
 constexpr int CDW = 49;                      // row stride of [C | D_v] (48 used: the 30 state columns and the 18 joint-velocity columns)
-constexpr int LDQ = 18, LDY = 34, LDT = 18, LDW = 17;
-constexpr int X_DOUBLES = 1152;
-constexpr int L_X = 0;                       // X: x u x_next x_ref [4][32] | Q_v [32][LDQ] + Y [16][LDY] | At [32][LDT] + Bt [32][LDT] | W tile [32][LDW]
-constexpr int L_XU = L_X, L_QS = L_X, L_YM = L_X + 32 * LDQ, L_AT = L_X, L_BT = L_X + 32 * LDT, L_WT = L_X;
-constexpr int L_PA = L_X + X_DOUBLES;        // rows 12..29 of Pall [18][PAW]  /  [C | D_v] [16][CDW]
+constexpr int LDQ = 18, LDY = 34;
+constexpr int X_DOUBLES = 18 * LDQ;
+constexpr int L_X = 0;                       // X: x u x_next dx [4][32] (+ fin[64] red[64]) | Q_v [18][LDQ]
+constexpr int L_XU = L_X, L_QS = L_X, L_FIN = L_X + 128, L_RED = L_X + 192;
+constexpr int L_PA = L_X + X_DOUBLES;        // rows 12..29 of Pall [18][PAW]  /  [C | D_v] [16][CDW]  /  Y [12][LDY]
+constexpr int L_YM = L_PA;
 constexpr int L_EEJ = L_PA + 18 * PAW;       // EE error Jacobian [6][32]
-constexpr int L_VEC = L_EEJ + 192;           // b[30] r[30] e[16] eeh[6] (+2) | fin[64] | pe[12] fb[36] ddp[6] ddv[6] (+4)
-constexpr int L_RED = L_VEC + 84 + 64 + 64;  // wavefront exchange scratch
-constexpr int RED_DOUBLES = 64;
-constexpr int LQ_LDS_DOUBLES = L_RED + RED_DOUBLES;
-static_assert(16 * CDW <= 18 * PAW && 32 * LDQ + 16 * LDY <= X_DOUBLES && 2 * 32 * LDT <= X_DOUBLES && 32 * LDW <= X_DOUBLES, "aliases must fit");
-static_assert(LQ_LDS_DOUBLES * sizeof(real) <= 20480, "eight nodes per CU");
+constexpr int L_VEC = L_EEJ + 192;           // b[30] r[30] e[16] eeh[6] (+2) | pe[12] fb[36] ddp[6] ddv[6] (+4) | q[30] (+2) | cost[30] (+2)
+constexpr int LQ_LDS_DOUBLES = L_VEC + 84 + 64 + 32 + 32;
+static_assert(16 * CDW <= 18 * PAW && 12 * LDY <= 18 * PAW && L_RED + 64 <= X_DOUBLES, "aliases must fit");
+static_assert(LQ_LDS_DOUBLES * sizeof(real) * 12 <= 160 * 1024, "twelve nodes per CU");
 
 // Both kernels of this file run one wavefront per workgroup: LDS hand-offs between lanes need no hardware barrier (a wavefront's
 // LDS operations complete in issue order), only the compiler fence QM_WAVE_SYNC() -- and, unlike __syncthreads(), that does not
@@ -53,9 +65,9 @@ __device__ __forceinline__ real waveSum(real* red, int lane, real v) {
 // ---- kernel 2: cost, projection, projected stage record
 // QM_LQ_EXTERN (the product build of qmgpu_api.hip): only declared here, defined in qmgpu_lq.hip, which is compiled at -O2 (measured 2.7 % faster; that file says how)
 #if defined(QM_LQ_EXTERN) && !defined(QM_RICCATI_TIMING)
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) lq_node_kernel(LqArgs a);
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) lq_node_kernel(LqArgs a);
 #else
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) lq_node_kernel(LqArgs a) {
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) lq_node_kernel(LqArgs a) {
   __shared__ real lds[LQ_LDS_DOUBLES];
   QM_POISON_LDS(lds, LQ_LDS_DOUBLES);
   const int lane = threadIdx.x;
@@ -69,10 +81,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const real* bcs = a.Rw + QM_RW_DERIVED;   // barrier constants (layout.h)
 
   real* PA = lds + L_PA; real* CD = lds + L_PA;
-  real* AT = lds + L_AT; real* BT = lds + L_BT; real* WT = lds + L_WT;
   real* EEJ = lds + L_EEJ; real* bv = lds + L_VEC; real* rv = bv + 30; real* ev = rv + 30; real* eeh = ev + 16;
-  real* fin = bv + 84; real* pev = fin + 64; real* fb = pev + 12; real* ddp = fb + 36; real* ddv = ddp + 6;
-  real* red = lds + L_RED;
+  real* pev = bv + 84; real* fb = pev + 12; real* ddp = fb + 36; real* ddv = ddp + 6; real* qv = bv + 148; real* cst = qv + 32;
+  real* fin = lds + L_FIN; real* red = lds + L_RED;
 
   QM_TICK_DECL;
   const real* tg = a.tgrid + size_t(inst) * (a.N + 1);
@@ -81,8 +92,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const real* xG = a.X + (size_t(inst) * (a.N + 1) + node) * 30;
   const real* uG = terminal ? a.zeros : a.U + (size_t(inst) * a.N + node) * 30;
   // x, u, x_next and the reference state are read many times with wave-uniform indices: one vector load each into LDS instead of
-  // chains of dependent scalar loads.  They live in region X and are dead before the QR publishes its factors there.
-  real* x = lds + L_XU; real* u = x + 32; real* xnext = x + 64; real* xref = x + 96;
+  // chains of dependent scalar loads.  They live in region X and are dead before the QR publishes Q_v there.
+  real* x = lds + L_XU; real* u = x + 32; real* xnext = x + 64; real* dx = x + 96;   // dx = x - x_ref
   const Schedule sched{a.schedNum[inst], a.schedTimes + size_t(inst) * QMGPU_MAX_EVENTS, a.schedModes + size_t(inst) * (QMGPU_MAX_EVENTS + 1)};
   const int phase = a.nodePhase[size_t(inst) * (a.N + 1) + node];
   const int mode = sched.modes[phase];
@@ -146,9 +157,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   real hf[3];   // f_e - f_ref (column 61 of the position rows, ad_node_kernel)
 #pragma unroll
   for (int q = 0; q < 3; ++q) hf[q] = ftOn ? ad[AD_EE + q * 64 + 61] : 0.0_r;
-  real phid[12], phiv[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) { phid[i] = ad[AD_PHI + i * 64 + lane]; phiv[i] = ad[AD_PHI + i * 64 + 60]; }
+  // lane i < 12: phi_i, the constant column of row i (the dense rows of [A | B] themselves are read from the AD rows where they are used:
+  // debug dump, products (1))
+  const real phiv = lane < 12 ? ad[AD_PHI + (lane < 12 ? lane : 0) * 64 + 60] : 0.0_r;
 
   // (the record stores stay ordinary stores: as streaming stores -- QM_STREAM_STORE, which ad_node_kernel uses for its rows -- they made this kernel slower,
   //  0.656 -> 0.686 ms, and streaming loads of the AD rows as well, 0.656 -> 0.676 ms; measured in round 3)
@@ -157,8 +168,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   int tIdx; real tAlpha;
   timeSegment(tTimes, a.K, t, tIdx, tAlpha);
   if (lane < 30) {
-    x[lane] = xG[lane]; u[lane] = uG[lane]; xnext[lane] = terminal ? xG[lane] : xG[30 + lane];
-    xref[lane] = xReference(tStates, a.K, tIdx, tAlpha, lane);
+    const real xl = xG[lane];
+    x[lane] = xl; u[lane] = uG[lane]; xnext[lane] = terminal ? xl : xG[30 + lane];
+    dx[lane] = xl - xReference(tStates, a.K, tIdx, tAlpha, lane);   // one LDS read per term of Q dx below, not two (they are all issued at once)
   }
   QM_WAVE_SYNC();
   const int c = lane;
@@ -180,12 +192,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
       real Qdx0 = 0.0_r, Qdx1 = 0.0_r;
 #pragma unroll
       for (int i = 0; i < 30; i += 2) {
-        Qdx0 += st.Q[i * 30 + c] * (x[i] - xref[i]);
-        Qdx1 += st.Q[(i + 1) * 30 + c] * (x[i + 1] - xref[i + 1]);
+        Qdx0 += st.Q[i * 30 + c] * dx[i];
+        Qdx1 += st.Q[(i + 1) * 30 + c] * dx[i + 1];
       }
       const real Qdx = Qdx0 + Qdx1;
       qc += Qdx;
-      costPart += 0.5_r * (x[c] - xref[c]) * Qdx;
+      costPart += 0.5_r * dx[c] * Qdx;
       if (c >= 24) {  // arm joint position soft box (QMInterface.cpp:177-219)
         const Barrier bp{st.joint_pos_barrier_mu, st.joint_pos_barrier_delta};
         const real lo = md.q_lower[c - 12], up = md.q_upper[c - 12];
@@ -199,6 +211,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     }
     if (c >= 24 && c < 30) ddp[c - 24] = dd;
     qc *= sc;
+    if (c < 30) { qv[c] = qc; cst[c] = costPart; }   // read back at the end: held in a register through the projection and the products, it pushed the kernel over 168 VGPRs
   }
   QM_WAVE_SYNC();
   // entry (i, j) of the state-cost Hessian (unscaled); i, j may be any lane-dependent indices < 32
@@ -225,8 +238,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll 6
       for (int i = 0; i < 30; ++i) { const real v = qEntry(i, c); rec[OFF_QT + i * 30 + c] = v; if (dbg) dbg[DBG_Q + i * 30 + c] = v; }
     }
-    const real nodeCost = waveSum(red, lane, costPart);
-    if (c < 30) { rec[OFF_qt + c] = qc; if (dbg) dbg[DBG_q + c] = qc; }
+    if (c < 30) { rec[OFF_qt + c] = qv[c]; if (dbg) dbg[DBG_q + c] = qv[c]; }
+    const real nodeCost = waveSum(red, lane, lane < 30 ? cst[lane] : 0.0_r);
     if (lane == 0) { real* m = a.metrics + (size_t(inst) * (a.N + 1) + node) * NODE_METRICS; m[0] = nodeCost; m[1] = 0.0_r; m[2] = 0.0_r; m[3] = 0.0_r; }
     return;
   }
@@ -235,12 +248,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   // ---- Jacobian of the RK2 map Phi = x + dt/2 (k1 + k2): rows 12.. are x_j + dt v_j exactly, so only the twelve momentum /
   //      base-pose rows of [A | B] are dense (phid).
   if (dbg && c < 60) {
-    for (int i = 0; i < 30; ++i) { const real v = i < 12 ? phid[i < 12 ? i : 0] + (c == i ? 1.0_r : 0.0_r) : (c == i ? 1.0_r : 0.0_r) + (c == 30 + i ? dt : 0.0_r); if (c < 30) dbg[DBG_A + i * 30 + c] = v; else dbg[DBG_B + i * 30 + (c - 30)] = v; }
+    for (int i = 0; i < 30; ++i) { const real v = i < 12 ? ad[AD_PHI + (i < 12 ? i : 0) * 64 + c] + (c == i ? 1.0_r : 0.0_r) : (c == i ? 1.0_r : 0.0_r) + (c == 30 + i ? dt : 0.0_r); if (c < 30) dbg[DBG_A + i * 30 + c] = v; else dbg[DBG_B + i * 30 + (c - 30)] = v; }
   }
-  if (lane == 0) {
-    for (int i = 0; i < 12; ++i) bv[i] = x[i] + phiv[i] - xnext[i];
-    for (int j = 0; j < 18; ++j) bv[12 + j] = x[12 + j] + dt * u[12 + j] - xnext[12 + j];
-  }
+  if (lane < 12) bv[lane] = x[lane] + phiv - xnext[lane];
+  else if (lane < 30) bv[lane] = x[lane] + dt * u[lane] - xnext[lane];
   QM_TICK(3);
   // ---- input cost: R' + friction-cone and arm-velocity barriers.  Lane c < 30 forms the gradient entry c and the barrier terms
   //      of its column; the terms go to LDS (fb: four 3x3 friction blocks, ddv: arm-velocity diagonal), R' itself stays in HBM / L1.
@@ -296,6 +307,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         fb[(fo + 0) * 3 + ac] = e0; fb[(fo + 1) * 3 + ac] = e1; fb[(fo + 2) * 3 + ac] = e2;
       }
       rv[c] = dt * rc;
+      cst[c] = costPart;   // (lanes >= 30 hold none: their share is 0) summed after products (1), as q~: not held in a register through the projection
     }
   }
   QM_WAVE_SYNC();
@@ -368,16 +380,18 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     }
   }
   QM_TICK(5);
-  // Pall operand of the matrix cores, element (k, j) with k = 4 ks + h (this lane's row of k step ks) and j = 16 tq + l16:
-  // rows k < 12 (force inputs, k steps 0..2) are synthesised -- Pe = pinned swing force in column 30, a unit entry in the Pu column
-  // of a free stance force --, rows 12..29 come from LDS, rows 30 and 31 are zero.
-  real peK[3]; int puK[3];
   {
     real peForce = 0.0_r;   // pinned swing-foot forces: Pe = -e_f
 #pragma unroll
     for (int i = 0; i < 12; ++i) if (lane == i && frcRowOf[i] >= 0) peForce = -ev[frcRowOf[i] >= 0 ? frcRowOf[i] : 0];
     if (lane < 12) pev[lane] = peForce;
     QM_WAVE_SYNC();
+  }
+  // Pall operand of the matrix cores, element (k, j) with k = 4 ks + h (this lane's row of k step ks) and j = 16 tq + l16:
+  // rows k < 12 (force inputs, k steps 0..2) are synthesised -- Pe = pinned swing force in column 30, a unit entry in the Pu column
+  // of a free stance force --, rows 12..29 come from LDS, rows 30 and 31 are zero.
+  real peK[3]; int puK[3];
+  {
 #pragma unroll
     for (int ks = 0; ks < 3; ++ks) {
       const int kk = 4 * ks + h;
@@ -473,19 +487,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         y[i] = sacc * qmReadLane(rinv, i);
       }
     }
-    // publish Y (rows k < 16, my column) and Q_v (lane 16 + c holds row c; rows 18..31 cleared) in region X
+    // publish Y (rows k < 12, my column; in region PA) and Q_v (lane 16 + c holds row c; in region X)
     real* Ym = lds + L_YM;
     real* Qs = lds + L_QS;
     if (lane < 32) {
 #pragma unroll
-      for (int k = 0; k < NCMAX; ++k) Ym[k * LDY + lane] = (k < NVMAX && lane <= 30) ? y[k < NVMAX ? k : 0] : 0.0_r;
+      for (int k = 0; k < NVMAX; ++k) Ym[k * LDY + lane] = lane <= 30 ? y[k] : 0.0_r;
     }
-    if (lane >= 16 && lane < 48) {
+    if (lane >= 16 && lane < 34) {
 #pragma unroll
-      for (int r = 0; r < 18; ++r) Qs[(lane - 16) * LDQ + r] = lane < 34 ? qcol[r] : 0.0_r;
+      for (int r = 0; r < 18; ++r) Qs[(lane - 16) * LDQ + r] = qcol[r];
     }
     QM_WAVE_SYNC();
-    // [Px | Pe] rows 12..29 = -Q_v1 Y on the matrix cores (K = 16 >= nv; rows of Y beyond nv are zero)
+    // [Px | Pe] rows 12..29 = -Q_v1 Y on the matrix cores (K = 16 >= nv; rows of Y beyond nv are zero).  Rows 18..31 of Q_v and rows
+    // 12..15 of Y are zero and not stored: the operands are synthesised with the values the stored zeros gave (-0 for A, +0 for B).
     QmAcc pc[4];
 #pragma unroll
     for (int t4 = 0; t4 < 4; ++t4)
@@ -493,11 +508,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
       for (int r = 0; r < 4; ++r) pc[t4][r] = 0.0_r;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      const int kk = 4 * ks + h;
-      const real a0 = -Qs[la * LDQ + kk], a1 = -Qs[(16 + la) * LDQ + kk];
-      const real b0 = Ym[kk * LDY + l16], b1 = Ym[kk * LDY + 16 + l16];
+      const int kk = 4 * ks + h, kY = kk < NVMAX ? kk : 0, rQ = 16 + la < 18 ? 16 + la : 16;
+      const real q0 = Qs[la * LDQ + kk], q1 = Qs[rQ * LDQ + kk], y0 = Ym[kY * LDY + l16], y1 = Ym[kY * LDY + 16 + l16];
+      const real a0 = -q0, a1 = -(16 + la < 18 ? q1 : 0.0_r);
+      const real b0 = kk < NVMAX ? y0 : 0.0_r, b1 = kk < NVMAX ? y1 : 0.0_r;
       qmMfma(pc[0], a0, b0); qmMfma(pc[1], a0, b1); qmMfma(pc[2], a1, b0); qmMfma(pc[3], a1, b1);
     }
+    QM_WAVE_SYNC();   // Y (region PA) is consumed: the Pall rows overwrite it
     // Pall: rows 0..11 (forces): Px = 0, Pu = unit columns of the free stance forces -- neither is stored (layout.h) --, Pe = pinned swing forces;
     //       rows 12..29 (joint velocities): [Px | Pe] from the tiles, Pu = Q_v2 (record and LDS)
     if (lane < 12) rec[OFF_PE + lane] = pev[lane];
@@ -537,32 +554,31 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const int nb = lane == 32 ? node - 1 : node + 1;
     rec[lane == 32 ? OFF_DTPREV : OFF_DTNEXT] = (nb >= 0 && nb < a.N) ? a.dtgrid[size_t(inst) * (a.N + 1) + nb] : 0.0_r;
   }
-  {  // transposed dense rows: At[j][i] = A[i][j], Bt[k][i] = B[i][k], i < 12 (columns 12..15 and rows 30,31 zero)
-    real* dst = (lane < 30) ? AT + lane * LDT : (lane < 60 ? BT + (lane - 30) * LDT : AT + 30 * LDT + (lane - 60) * LDT);
-    const bool pad = lane >= 60;  // lanes 60..61 clear rows 30,31 of At; lanes 62..63 rows 30,31 of Bt
-    if (lane >= 62) dst = BT + (30 + lane - 62) * LDT;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) dst[i] = (!pad && i < 12) ? phid[i < 12 ? i : 0] + ((lane < 30 && lane == i) ? 1.0_r : 0.0_r) : 0.0_r;
-  }
-  QM_WAVE_SYNC();
 
   QM_TICK(7);
   // ================================================================== products on the fp64 matrix cores
-  // (1) rows 0..11 of [A~ | b~ | B~] = [A | b | 0] + B Pall
+  // (1) rows 0..11 of [A~ | b~ | B~] = [A | b | 0] + B Pall.  The dense rows i < 12 of [A | B] are [Phi' + I | Phi'] with Phi' the AD
+  //     rows (AD_PHI: columns 0..29 A, 30..59 B): accumulator and operand entries are loaded from there (cache resident).
   const int nTn = nt > 16 ? 4 : 3;   // 16-column tiles of Pall in use
   {
     QmAcc c1[4];
+    real araw[4][3], ab[8];   // (no QM_KEEP here: holding all twenty at once pushed the kernel over 168 VGPRs)
+#pragma unroll
+    for (int tn = 0; tn < 4; ++tn)
+#pragma unroll
+      for (int r = 0; r < 3; ++r) araw[tn][r] = ad[AD_PHI + (h + 4 * r) * 64 + tn * 16 + l16];   // A[i][j] - (i == j), i = h + 4 r < 12
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) { const int k = 4 * ks + h; ab[ks] = ad[AD_PHI + (la < 12 ? la : 0) * 64 + 30 + (k < 30 ? k : 0)]; }   // B[la][k]
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) { const int k = 4 * ks + h; ab[ks] = (la < 12 && k < 30) ? ab[ks] : 0.0_r; }
 #pragma unroll
     for (int tn = 0; tn < 4; ++tn)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = h + 4 * r, j = tn * 16 + l16;
-        const real av = AT[(j < 32 ? j : 0) * LDT + i], bb = bv[i < 30 ? i : 0];
+        const real av = r < 3 ? araw[tn][r < 3 ? r : 0] + (j == i ? 1.0_r : 0.0_r) : 0.0_r, bb = bv[i < 30 ? i : 0];
         c1[tn][r] = (i < 12) ? (j < 30 ? av : (j == 30 ? bb : 0.0_r)) : 0.0_r;
       }
-    real ab[8];
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) ab[ks] = BT[(4 * ks + h) * LDT + la];
 #pragma unroll
     for (int tn = 0; tn < 4; ++tn) {
       if (tn < nTn) {
@@ -587,17 +603,17 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
       }
     }
   }
-  QM_WAVE_SYNC();   // every lane has consumed At / Bt: region X becomes the W tile
-  const real nodeCost = dt * waveSum(red, lane, costPart);
+  QM_WAVE_SYNC();
+  const real nodeCost = dt * waveSum(red, lane, lane < 30 ? cst[lane] : 0.0_r);
   if (lane == 0) {
     real* m = a.metrics + (size_t(inst) * (a.N + 1) + node) * NODE_METRICS;
     m[0] = nodeCost; m[1] = dt * dynSq; m[2] = dt * eqSq; m[3] = 0.0_r;
   }
-  if (dbg && c < 30) { for (int i = 0; i < 30; ++i) dbg[DBG_Q + i * 30 + c] = sc * qEntry(i, c); dbg[DBG_q + c] = qc; }
+  if (dbg && c < 30) { for (int i = 0; i < 30; ++i) dbg[DBG_Q + i * 30 + c] = sc * qEntry(i, c); dbg[DBG_q + c] = qv[c]; }
 
   QM_TICK(8);
-  // (2) W = R Pall and (3) G = Pall^T W, [Q~ | P~^T; P~ | R~] = [Q | 0; 0 | 0] + G, one 16-column tile of W at a time: the tile goes
-  // through LDS (accumulator layout -> operand layout) and is consumed by the tiles (tm, tn) of G that the record needs:
+  // (2) W = R Pall and (3) G = Pall^T W, [Q~ | P~^T; P~ | R~] = [Q | 0; 0 | 0] + G, one 16-column tile of W at a time: the tile stays
+  // in its accumulator registers (they are already the B operand layout) and is consumed by the tiles (tm, tn) of G that the record needs:
   //   tn = 0, 1: tm = 0, 1 (state block, row 30 carries Pe^T R Px), 2 and 3 (P~; tm = 3 only when m~ > 16)
   //   tn = 2, 3: tm = 2, 3 (R~; column 30 of tn = 1 carries Pu^T R Pe)
   // Row 30 of W is r^T Pall; together with row / column 30 of G it completes q~ and r~ (fin).
@@ -638,9 +654,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
           for (int ks = (tn == 0 ? 3 : 0); ks < 8; ++ks) { qmMfma(wA, r0[ks], pb[ks]); qmMfma(wB, r1[ks], pb[ks]); }   // (force rows of Pall: zero in columns 0..15)
         }
-        QM_WAVE_SYNC();   // the previous tile's readers are done
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { const int i = h + 4 * r; WT[i * LDW + l16] = wA[r]; WT[(16 + i) * LDW + l16] = wB[r]; }
+        QM_WAVE_SYNC();   // the previous tile's fin updates are done
         if (h == 2) fin[tn * 16 + l16] += wB[3];  // row 30 of W
         QM_WAVE_SYNC();
         const bool top = tn < 2;         // tiles tm = 0, 1
@@ -684,9 +698,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             qmMfma(g[0], wq * e0[ks], on ? ej[ks] : 0.0_r); qmMfma(g[1], wq * e1[ks], on ? ej[ks] : 0.0_r);
           }
         }
-        real wb[8];
+        real wb[8];   // B operand W[4 ks + h][l16]: accumulator register r of wA (wB) holds row h + 4 r (16 + h + 4 r) of the tile
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) wb[ks] = WT[(4 * ks + h) * LDW + l16];
+        for (int ks = 0; ks < 8; ++ks) wb[ks] = ks < 4 ? wA[ks & 3] : wB[ks & 3];
 #pragma unroll
         for (int tm = 0; tm < 4; ++tm) {
           if ((tm < 2 && top) || tm == 2 || (tm == 3 && low3)) {
@@ -722,7 +736,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     }
   }
   QM_WAVE_SYNC();
-  if (isX) rec[OFF_qt + lane] = qc + fin[lane];
+  if (isX) rec[OFF_qt + lane] = qv[lane] + fin[lane];
   else if (isU) rec[OFF_rt + (lane - 32)] = fin[lane];
   QM_TICK(9);
   // zero padding of B~, Pu (above) and r~ beyond m~ columns: the forward sweep of riccati_kernel multiplies whole MT-wide rows

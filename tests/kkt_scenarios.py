@@ -1,0 +1,261 @@
+"""Scenarios of the one-step KKT checks and the check itself, shared by the CPU tier (test_kkt_reference.py: the oracle on every scenario, the host-emulated
+kernels on a reduced set) and the GPU tier (test_gpu_kkt.py: the product on every scenario).
+
+A scenario is one batch of ONE SQP iteration: the inputs of qmgpu_mpc_solve_batch, the iterate the solver linearises at (the warm start it is given, or the
+initializer's x_k = x0, u_k = weight compensation) and whether the line search runs.  The check compares the solver's step X_out - X, U_out - U with alpha times
+the step of kkt_reference solved from the solver's OWN LQ blocks (alpha = stats[4]), and those blocks with the oracle's at every node.
+
+Tolerance rule (measured against the reference, never against the code under test).  Per scenario and separately for dX and dU:
+    e_orc = max over instances of the oracle's step error against the reference built from the oracle's blocks,
+    e_lu  = max over instances of the plain fp64 LU solution's error against the refined one,
+    tol   = 10 * max(e_orc, e_lu)                       (rel-inf, kkt_reference.rel_err),
+and every instance passes if |step - alpha d_ref|_inf <= tol * |alpha d_ref|_inf + 2 eps max(|X|_inf, |X_out|_inf), the last term the rounding of the final
+X + alpha dX (U alike).  Both the product and the oracle are backward-stable fp64 implementations of the same factorisation that differ in summation order only;
+a wrong term shows at its own size, orders of magnitude above this.  The refinement's last correction must stay below 1e-2 tol, so that the reference's own
+error cannot use up the margin.
+"""
+import json
+import os
+
+import numpy as np
+
+import kkt_reference as KR
+import support as S
+from qm_door_amd import abi, api
+
+FACTOR = 10.0
+BLOCK_KEYS = ("A", "B", "b", "Q", "R", "q", "r", "C", "D", "e")
+# the constraint counts of the four factorisation unrolls of lq_node_kernel (m~ = 30 - nc = 18, 17, 16 / 18, 14 / 16) as these schedules produce them
+GAIT_NC = {"stance": {12}, "static_walk": {13}, "trot": {12, 14}, "flying_trot": {14, 16}}
+GAIT_PHASE0 = {"stance": 0.0, "static_walk": 0.0, "trot": 0.03, "flying_trot": -0.2}     # flying trot: LF_RH, then flight from t = 0.05
+
+
+class Scenario:
+    def __init__(self, name, x0, tt, ts, nev, ev, md, grid, X, U, warm, line_search, uniform=True, contact=None, nc=None):
+        self.name, self.B, self.N = name, x0.shape[0], grid.shape[1] - 1
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+        self.x0, self.tt, self.ts, self.grid, self.X, self.U = f64(x0), f64(tt), f64(ts), f64(grid), f64(X), f64(U)
+        self.nev = np.ascontiguousarray(nev, dtype=np.int32)
+        self.ev, self.md = f64(ev), np.ascontiguousarray(md, dtype=np.int32)
+        self.contact = None if contact is None else f64(contact)
+        self.warm, self.line_search, self.uniform, self.nc = warm, line_search, uniform, nc
+        assert np.array_equal(self.X[:, 0], self.x0)                     # the solvers overwrite X[0] with x0 before they linearise: dx_0 = 0
+
+    def instance(self, i):
+        """(grid, nev, ev, md, tt, ts) of instance i, as the oracle takes them"""
+        return self.grid[i], int(self.nev[i]), self.ev[i], self.md[i], self.tt[i], self.ts[i]
+
+
+def force_tracking_interface(lib=None):
+    """the interface of the force-tracking scenario (test_force_tracking.py: contact stiffness and force weight switched on)"""
+    itf = api.QMInterface(lib=lib) if lib is not None else api.QMInterface()
+    itf.problem.settings.ee_contact_stiffness = S.FT_STIFFNESS
+    itf.problem.settings.ee_force_mu = S.FT_MU
+    return itf
+
+
+def gait_schedule(itf, gait, t_end):
+    return api.GaitSchedule(lib=itf.lib).mode_schedule(gait, GAIT_PHASE0[gait], 0.0, t_end)
+
+
+def cold_iterate(itf, oracle, x0, grid, nev, ev, md):
+    """the initializer's guess (QMInitializer.cpp:33-41): x_k = x0, u_k = weight compensation of the node's mode"""
+    N = len(grid) - 1
+    X, U = np.repeat(x0[None, :], N + 1, axis=0), np.zeros((N, 30))
+    weight = itf.robot_mass * itf.problem.settings.gravity
+    for k in range(N):
+        mode = oracle.node_mode_at(ev[:nev], md[:nev + 1], grid[k])
+        legs = [c for c in range(4) if (mode >> (3 - c)) & 1]
+        for c in legs:
+            U[k, 3 * c + 2] = weight / len(legs)
+    return X, U
+
+
+def defect_iterate(itf, oracle, x0, grid, nev, ev, md, rng):
+    """a warm start off the dynamics (defects b != 0 at every node) with perturbed forces and joint rates"""
+    X, U = cold_iterate(itf, oracle, x0, grid, nev, ev, md)
+    X[1:] += 0.01 * rng.standard_normal(X[1:].shape)
+    U += rng.standard_normal(U.shape) * np.r_[np.full(12, 2.0), np.full(18, 0.1)]
+    return X, U
+
+
+def _batch(name, itf, oracle, gaits, N, seed, warm, line_search, grid=None, x0=None, tt=None, ts=None, contact=None, nc=None):
+    """instances i = 0.. B-1 on the schedules of gaits[i]; uniform grid (t0 = 0) unless `grid` is given"""
+    B = len(gaits)
+    dt = itf.problem.settings.dt
+    rng = np.random.default_rng(seed)
+    uniform = grid is None
+    g = np.arange(N + 1) * dt if uniform else grid
+    x0 = S.perturbed_states(itf.initial_state, B, seed=seed) if x0 is None else x0
+    if tt is None:
+        tgt = S.nominal_target(oracle, itf.initial_state)
+        tt, ts = np.zeros((B, 1)), np.tile(tgt, (B, 1, 1)).copy()
+    nev, ev, md = np.zeros(B, dtype=np.int32), np.zeros((B, abi.MAX_EVENTS)), np.zeros((B, abi.MAX_EVENTS + 1), dtype=np.int32)
+    X, U = np.zeros((B, N + 1, 30)), np.zeros((B, N, 30))
+    for i, gait in enumerate(gaits):
+        nev[i], ev[i], md[i] = gait_schedule(itf, gait, g[-1] + 1.0) if isinstance(gait, str) else gait
+        X[i], U[i] = (defect_iterate(itf, oracle, x0[i], g, nev[i], ev[i], md[i], rng) if warm else cold_iterate(itf, oracle, x0[i], g, nev[i], ev[i], md[i]))
+    return Scenario(name, x0, tt, ts, nev, ev, md, np.tile(g, (B, 1)), X, U, warm, line_search, uniform, contact, nc)
+
+
+def unroll(itf, oracle, gait, B, N, seed, warm, line_search):
+    return _batch(gait, itf, oracle, [gait] * B, N, seed, warm, line_search, nc=GAIT_NC[gait])
+
+
+def mixed_gaits(itf, oracle, B, N, seed=21):
+    gaits = list(GAIT_NC)
+    return _batch(f"mixed_gaits_B{B}_N{N}", itf, oracle, [gaits[i % 4] for i in range(B)], N, seed, True, True, nc=set().union(*GAIT_NC.values()))
+
+
+def event_grid(itf, oracle, horizon, B=2, seed=23):
+    """the shooting grid with the mode switches as nodes (qmgpu_time_grid_with_events): the first switch 2.5 ms after a node, so one step is dt / 6"""
+    dt = itf.problem.settings.dt
+    nev, ev, md = S.trot_schedule(horizon + 1.0, phase0=3 * dt + 0.0025)
+    N, grid = api.time_grid_with_events(0.0, horizon, dt, ev[:nev], lib=itf.lib)
+    assert (np.diff(grid) < 0.25 * dt).any()
+    return _batch("event_grid", itf, oracle, [(nev, ev, md)] * B, N, seed, True, False, grid=grid)
+
+
+def barrier(itf, oracle):
+    """relaxed barriers in their quadratic branches, three distinct target knots (support.relaxed_barrier_batch, the construction of test_gpu_edges.py)"""
+    x0, tt, ts, nev, ev, md, X, U = S.relaxed_barrier_batch(itf, oracle)
+    B, N = X.shape[0], X.shape[1] - 1
+    grid = np.tile(np.arange(N + 1) * itf.problem.settings.dt, (B, 1))
+    return Scenario("barrier", x0, tt, ts, np.full(B, nev), np.tile(ev, (B, 1)), np.tile(md, (B, 1)), grid, X, U, True, True)
+
+
+def force_tracking(itf_ft, oracle_ft, B=2, N=20):
+    """door opening (support.door_opening_batch): the end-effector contact model and the force soft constraint in every intermediate node"""
+    dt = itf_ft.problem.settings.dt
+    x0, tt, ts, contact = S.door_opening_batch(oracle_ft, itf_ft.initial_state, B, seed=2, t_end=N * dt)
+    return _batch("force_tracking", itf_ft, oracle_ft, ["trot"] * B, N, 2, False, True, x0=x0, tt=tt, ts=ts, contact=contact)
+
+
+def horizon(itf, oracle, N, warm, line_search, B=2):
+    return _batch(f"horizon_N{N}", itf, oracle, ["trot"] * B, N, 30 + N, warm, line_search)
+
+
+# ------------------------------------------------------------------------------------------------ the scenario lists
+def gpu_scenarios():
+    """name -> builder(itf, oracle): every scenario of the GPU tier (the force-tracking builder takes the force-tracking interface and oracle)"""
+    return {
+        "stance": lambda itf, orc: unroll(itf, orc, "stance", 2, 30, 11, True, False),
+        "static_walk": lambda itf, orc: unroll(itf, orc, "static_walk", 2, 30, 12, True, False),
+        "trot_cold": lambda itf, orc: unroll(itf, orc, "trot", 2, 30, 13, False, False),
+        "flying_trot": lambda itf, orc: unroll(itf, orc, "flying_trot", 2, 30, 14, True, True),
+        "mixed_gaits": lambda itf, orc: mixed_gaits(itf, orc, 4, 40),
+        "event_grid": lambda itf, orc: event_grid(itf, orc, 0.6),
+        "barrier": barrier,
+        "force_tracking": force_tracking,
+        "horizon_N1": lambda itf, orc: horizon(itf, orc, 1, False, False),
+        "horizon_N2": lambda itf, orc: horizon(itf, orc, 2, True, True),
+        "horizon_N200": lambda itf, orc: horizon(itf, orc, 200, True, True),
+        "horizon_N300": lambda itf, orc: horizon(itf, orc, 300, False, True),
+        "batch_beyond_cus": lambda itf, orc: mixed_gaits(itf, orc, 300, 10, seed=25),
+    }
+
+
+def emu_scenarios():
+    """the reduced set of the host-emulated kernels: each factorisation unroll at N = 6..8, one event grid, one barrier case"""
+    return {
+        "stance": lambda itf, orc: unroll(itf, orc, "stance", 2, 6, 11, True, False),
+        "static_walk": lambda itf, orc: unroll(itf, orc, "static_walk", 2, 7, 12, True, True),
+        "trot_cold": lambda itf, orc: unroll(itf, orc, "trot", 2, 8, 13, False, False),
+        "flying_trot": lambda itf, orc: unroll(itf, orc, "flying_trot", 2, 8, 14, True, True),
+        "event_grid": lambda itf, orc: event_grid(itf, orc, 0.12),
+        "barrier": barrier,
+    }
+
+
+def build(registry, name, itf, oracle):
+    """scenario `name` of a list above, named as there"""
+    sc = registry[name](itf, oracle)
+    sc.name = name
+    return sc
+
+
+# ------------------------------------------------------------------------------------------------ the checks
+def _contact(oracle, sc, i):
+    if sc.contact is not None:
+        oracle.set_ee_contact_ref(sc.contact[i])
+
+
+def oracle_errors(sc, oracle, i, blocks=None):
+    """reference from the oracle's blocks of instance i and the oracle's own step on them (mpc_solve warm = the iterate, no line search)"""
+    grid, nev, ev, md, tt, ts = sc.instance(i)
+    X, U = sc.X[i], sc.U[i]
+    _contact(oracle, sc, i)
+    try:
+        ob = KR.oracle_blocks(oracle, grid, X, U, nev, ev, md, tt, ts) if blocks is None else blocks
+        step = oracle.mpc_solve(sc.N, grid[0], X[0], tt, ts, nev, ev, md, warm=(X, U), line_search=False, time_grid=grid)
+    finally:
+        oracle.set_ee_contact_ref(None)
+    ref = KR.solve(ob)
+    assert step["stats"][7] == 0 and step["stats"][4] == 1.0, (sc.name, i)
+    e_orc = (KR.rel_err(step["X"] - X, ref["dX"]), KR.rel_err(step["U"] - U, ref["dU"]))
+    e_lu = (KR.rel_err(ref["dX_lu"], ref["dX"]), KR.rel_err(ref["dU_lu"], ref["dU"]))
+    return dict(blocks=ob, ref=ref, step=step, e_orc=e_orc, e_lu=e_lu)
+
+
+def tolerance(per_instance):
+    """(tol_dX, tol_dU) of a scenario from the per-instance e_orc / e_lu"""
+    return tuple(FACTOR * max(max(p["e_orc"][j] for p in per_instance), max(p["e_lu"][j] for p in per_instance)) for j in (0, 1))
+
+
+def assert_blocks(sc, oracle_blocks_i, product_lq, i):
+    """nc and every LQ block of instance i at every node against the oracle (the 1e-10 bar of test_lq_blocks_match_oracle)"""
+    N = sc.N
+    for k in range(N + 1):
+        g, o = product_lq(i, k), oracle_blocks_i[k]
+        assert g["nc"] == o["nc"], (sc.name, i, k, g["nc"], o["nc"])
+        for key in (("Q", "q") if k == N else BLOCK_KEYS):
+            assert np.abs(g[key] - o[key]).max() <= 1e-10 * max(1.0, np.abs(o[key]).max()), (sc.name, i, k, key)
+
+
+def check_product(sc, oracle, out, product_lq, record_path=None):
+    """The product's step of scenario sc (out: T X U mode stats [B][..] of the solve, product_lq(i, k): its debug dump) against the reference from its own
+    blocks, under the tolerance rule of this module.  Every figure is measured (and recorded under record_path) before anything is asserted."""
+    B, N = sc.B, sc.N
+    eps = np.finfo(np.float64).eps
+    rows, gblocks = [], []
+    for i in range(B):
+        o = oracle_errors(sc, oracle, i)
+        gb = [product_lq(i, k) for k in range(N + 1)]
+        gref = KR.solve(gb)
+        alpha = float(out["stats"][i][4])
+        X, U, Xo, Uo = sc.X[i], sc.U[i], out["X"][i], out["U"][i]
+        ex, eu = np.abs((Xo - X) - alpha * gref["dX"]).max(), np.abs((Uo - U) - alpha * gref["dU"]).max()
+        sx, su = alpha * np.abs(gref["dX"]).max(), alpha * np.abs(gref["dU"]).max()
+        rows.append(dict(o, gref=gref, alpha=alpha, err=(ex, eu), scale=(sx, su),
+                         allow=(2 * eps * max(np.abs(X).max(), np.abs(Xo).max()), 2 * eps * max(np.abs(U).max(), np.abs(Uo).max())),
+                         e_lu=tuple(max(o["e_lu"][j], KR.rel_err((gref["dX_lu"], gref["dU_lu"])[j], (gref["dX"], gref["dU"])[j])) for j in (0, 1)),
+                         nc=sorted({int(b["nc"]) for b in gb[:N]})))
+        gblocks.append(gb)
+    tol = tolerance(rows)
+    rec = dict(instances=B, N=N, line_search=bool(sc.line_search), warm=bool(sc.warm), alpha=sorted({r["alpha"] for r in rows}),
+               nc=sorted(set().union(*[r["nc"] for r in rows])),
+               e_orc=[max(r["e_orc"][j] for r in rows) for j in (0, 1)], e_lu=[max(r["e_lu"][j] for r in rows) for j in (0, 1)],
+               product=[max(r["err"][j] / r["scale"][j] for r in rows) for j in (0, 1)], tolerance=list(tol),
+               correction=[max(max(r["ref"]["correction"][j], r["gref"]["correction"][j]) for r in rows) for j in (0, 1)])
+    print(sc.name, json.dumps(rec))
+    if record_path:
+        os.makedirs(os.path.dirname(os.path.abspath(record_path)), exist_ok=True)
+        try:
+            allrec = json.load(open(record_path))
+        except (OSError, ValueError):
+            allrec = {}
+        allrec[sc.name] = rec
+        json.dump(allrec, open(record_path, "w"), indent=1)
+    # ---- assertions
+    assert (out["stats"][:, 7] == 0).all(), sc.name
+    assert np.array_equal(out["T"], sc.grid), sc.name
+    if sc.nc is not None:
+        assert set(rec["nc"]) == set(sc.nc), (sc.name, rec["nc"])
+    for i, r in enumerate(rows):
+        assert_blocks(sc, r["blocks"], lambda ii, k: gblocks[ii][k], i)
+        a = r["alpha"]
+        assert a == 1.0 if not sc.line_search else (0 < a <= 1 and a == 2.0 ** np.round(np.log2(a))), (sc.name, i, a)
+        for j, part in enumerate(("dX", "dU")):
+            assert max(r["ref"]["correction"][j], r["gref"]["correction"][j]) <= 1e-2 * tol[j], (sc.name, i, part, r["ref"]["correction"], r["gref"]["correction"], tol)
+            assert r["err"][j] <= tol[j] * r["scale"][j] + r["allow"][j], (sc.name, i, part, r["err"][j] / r["scale"][j], tol[j])
+    return rec

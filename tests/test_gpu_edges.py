@@ -112,41 +112,7 @@ def test_relaxed_barrier_quadratic_branches_and_distinct_target_knots(interface,
     import gpu_harness as G
     B, N = 4, 12
     dt = interface.problem.settings.dt
-    md_ = interface.problem.model
-    x_nom, m = interface.initial_state, interface.robot_mass
-    x0 = S.perturbed_states(x_nom, B, seed=9)
-    up = np.array([md_.q_upper[12 + i] for i in range(6)]); lo = np.array([md_.q_lower[12 + i] for i in range(6)])
-    x0[0, 24] = up[0] - 5e-4; x0[0, 25] = lo[1] + 2e-4           # inside the delta band
-    x0[1, 26] = up[2]; x0[1, 27] = lo[3]                         # exactly on the limits
-    x0[2, 24] = up[0] + 0.02; x0[2, 28] = lo[4] - 0.01           # beyond
-    tgt = S.nominal_target(oracle, x_nom)
-    # three distinct knots: base moves and yaws, the EE target moves and rotates about two different axes
-    K = 3
-    tt = np.tile(np.array([0.0, 0.08, 0.2]), (B, 1))
-    ts = np.tile(tgt, (B, K, 1)).copy()
-    ts[:, 1, 6] += 0.05; ts[:, 2, 6] += 0.12; ts[:, 2, 9] += 0.2
-    ts[:, 1, 30:33] += [0.03, -0.02, 0.04]; ts[:, 2, 30:33] += [0.08, 0.05, -0.03]
-    def quat(axis, ang):
-        a = np.asarray(axis, float); a /= np.linalg.norm(a)
-        return np.r_[a * np.sin(ang / 2), np.cos(ang / 2)]
-    ts[:, 1, 33:37] = quat([0, 1, 0.2], 0.5); ts[:, 2, 33:37] = quat([1, 0.3, 0], -0.8)
-    nev, ev, md = S.trot_schedule(N * dt + 1.0, phase0=0.05)
-    # warm start: states = x0 held, inputs with starved / pulling stance feet and arm rates beyond their bounds
-    X = np.repeat(x0[:, None, :], N + 1, axis=1)
-    U = np.zeros((B, N, 30))
-    for i in range(B):
-        for k in range(N):
-            mode = oracle.node_mode_at(ev[:nev], md[:nev + 1], k * dt)
-            flags = [(mode >> (3 - c)) & 1 for c in range(4)]
-            st = [c for c in range(4) if flags[c]]
-            for c in st:
-                U[i, k, 3 * c + 2] = m * 9.81 / len(st)
-            U[i, k, 3 * st[0] + 2] = 3.0 + i                    # h = 0.7 * 3 - 5 < delta: quadratic branch
-            U[i, k, 3 * st[0]] = 4.0
-            if i == 3:
-                U[i, k, 3 * st[-1] + 2] = -6.0                  # pulling on the ground: h < 0
-    al = np.array([interface.problem.settings.arm_vel_lower[i] for i in range(6)]); au = np.array([interface.problem.settings.arm_vel_upper[i] for i in range(6)])
-    U[0, :, 24] = au[0] + 0.05; U[1, :, 26] = al[2] - 0.2; U[2, :, 29] = au[5] - 4e-4
+    x0, tt, ts, nev, ev, md, X, U = S.relaxed_barrier_batch(interface, oracle, B, N)
     sol = G.make_solver(interface, B, N)
     sol.enable_debug(True)
     mb = G.MpcBatch(x0, tt, ts, np.full(B, nev, dtype=np.int32), np.tile(ev, (B, 1)), np.tile(md, (B, 1)), N, warm=(X, U))

@@ -13,6 +13,10 @@
  *   qmgpu_mpc_solve_batch   <-> ocs2::MPC_BASE::run -> SqpSolver::runImpl, one SQP iteration
  *                               (object built at qm_controllers/src/QMController.cpp:288-289)
  *   qmgpu_policy_eval_batch <-> MPC_MRT_Interface::evaluatePolicy (QMController.cpp:134-142)
+ *   qmgpu_mpc_feedback_batch <-> the LinearController upstream's SqpSolver returns with sqp.useFeedbackPolicy
+ *                               (qm_controllers/config/task.info:90; multiple_shooting::remapProjectedGain + toPrimalSolution)
+ *   qmgpu_policy_eval_feedback_batch <-> LinearController::computeInput behind MRT_BASE::evaluatePolicy
+ *                               (same call site, QMController.cpp:134-142)
  *   qmgpu_warm_start_batch  <-> upstream SqpSolver::runImpl's initial guess from the previous PrimalSolution
  *                               (the solver object built at QMController.cpp:288-289 keeps it between runs)
  *   qmgpu_wbc_solve_batch   <-> qm::WbcBase::update / HierarchicalWbc::update
@@ -97,7 +101,9 @@ typedef struct qmgpu_settings {
   /* sqp + mpc (task.info:76-93,139-149); alpha_decay/alpha_min/gamma_c/armijo are OCS2 defaults */
   double dt, time_horizon, delta_tol, g_max, g_min, alpha_decay, alpha_min, gamma_c, armijo_factor;
   double cost_tol;                     /* sqp.costTol (upstream default 1e-4): convergence test between SQP iterations */
-  int32_t sqp_iterations, reserved0;
+  int32_t sqp_iterations;
+  int32_t use_feedback_policy;         /* sqp.useFeedbackPolicy (task.info:90, default false).  Changes nothing inside the library: a host reads it to decide
+                                          whether to call qmgpu_mpc_feedback_batch after a solve (adapters/GpuMpc.h does) */
   /* cost (task.info:193-288) */
   double initial_state[QMGPU_NX];
   double Q[QMGPU_NX * QMGPU_NX];
@@ -189,8 +195,8 @@ int qmgpu_synchronize(qmgpu_handle h);
  * its WBC in different threads, QMController.cpp:116-157 / 316-327) then fill those CUs.  With the option on, the WBC outputs of a cycle (out, out_status, input_last, working_set)
  * are complete after qmgpu_synchronize, or on the handle's stream after qmgpu_join_wbc (a device-side wait, no host wait) -- NOT after the caller synchronises its own stream.
  * Which calls join by themselves: qmgpu_cycle_batch (before its policy evaluation), qmgpu_wbc_solve_batch, qmgpu_set_stream (the NEW stream waits), qmgpu_set_overlap,
- * qmgpu_update_settings, qmgpu_debug_poison, qmgpu_synchronize, qmgpu_destroy.  Which do NOT: qmgpu_mpc_solve_batch, qmgpu_policy_eval_batch, qmgpu_frontend_batch,
- * qmgpu_warm_start_batch, qmgpu_gait_schedule_batch, qmgpu_get_input_weight, qmgpu_pack_results -- they touch nothing the library owns that a pending WBC reads or writes, and run next to it.
+ * qmgpu_update_settings, qmgpu_debug_poison, qmgpu_synchronize, qmgpu_destroy.  Which do NOT: qmgpu_mpc_solve_batch, qmgpu_policy_eval_batch, qmgpu_mpc_feedback_batch, qmgpu_policy_eval_feedback_batch,
+ * qmgpu_frontend_batch, qmgpu_warm_start_batch, qmgpu_gait_schedule_batch, qmgpu_get_input_weight, qmgpu_pack_results -- they touch nothing the library owns that a pending WBC reads or writes, and run next to it.
  * The pending WBC still READS the caller's rbd_measured / period / time (and ee_force) of that cycle and reads and writes input_last / working_set: those buffers must not
  * be modified -- by the caller's own kernels or copies on any stream, or through a non-joining call above -- until qmgpu_join_wbc, qmgpu_synchronize, or the next
  * qmgpu_cycle_batch / qmgpu_wbc_solve_batch has been issued on the handle. */
@@ -252,6 +258,31 @@ int qmgpu_mpc_solve_batch(qmgpu_handle h, const qmgpu_mpc_args* args);
 int qmgpu_policy_eval_batch(qmgpu_handle h, int batch, int num_nodes, const double* t_grid, const double* X,
                             const double* U, const int32_t* modes, const double* t_eval, double* x_out /*[batch][30]*/,
                             double* u_out /*[batch][30]*/, int32_t* mode_out /*[batch]*/);
+
+/* The SQP feedback policy.  Replaces the LinearController upstream's SqpSolver returns when sqp.useFeedbackPolicy is set (multiple_shooting::remapProjectedGain,
+ * then toPrimalSolution with gains): per node a 30 x 30 gain and a bias such that, near the planned trajectory, the optimal input for a state x at t_k is
+ *     u = uff_k + K_k x,        K_k = Px_k + Pu_k K~_k  (row-major; the Riccati gain of the projected problem mapped back to the full input),
+ *                               uff_k = U_k - K_k X_k   (so that x = X_k returns the planned input U_k),           k = 0 .. N-1
+ *     K_N = K_{N-1},  uff_N = uff_{N-1}                 (upstream repeats the last entry: the arrays are as long as the time grid).
+ * X, U: out_x / out_u of the solve (device pointers, as K, uff, status).  K_k is the sensitivity of the first input of the QP over nodes k .. N to its initial
+ * state.  Rows 0..11 (contact forces) of a swing foot are zero.
+ * Valid after a qmgpu_mpc_solve_batch / qmgpu_cycle_batch with QMGPU_ALG_SQP on the same QMGPU_F64 handle with the same batch and num_nodes; anything else
+ * (no solve yet, another shape, a QMGPU_ALG_DDP solve, a QMGPU_F32 handle) returns QMGPU_ERR_INVALID_ARGUMENT.  With sqp.sqpIteration > 1 the gains of an instance
+ * belong to the last iteration it performed, the one its out_x / out_u come from.
+ * An instance whose solve was flagged (out_stats[7] != 0) gets the feed-forward policy K = 0, uff = U and status[i] != 0; status[i] = 0 otherwise.
+ * Enqueued on the handle's stream, no host synchronisation; reads only what the library owns plus X, U.  Does not join a WBC pending on the overlap stream. */
+int qmgpu_mpc_feedback_batch(qmgpu_handle h, int batch, int num_nodes, const double* X /*[batch][N+1][30]*/, const double* U /*[batch][N][30]*/,
+                             double* K /*[batch][N+1][30][30]*/, double* uff /*[batch][N+1][30]*/, int32_t* status /*[batch] or NULL*/);
+
+/* qmgpu_policy_eval_batch for the feedback policy.  Replaces LinearController::computeInput behind MRT_BASE::evaluatePolicy (QMController.cpp:134-142): uff and K
+ * are interpolated linearly at t_eval exactly like U there (same interval, same weight, end values held), then
+ *     u_out = uff(t) + K(t) x_measured.
+ * x_out and mode_out are bit-identical to qmgpu_policy_eval_batch's.  All device pointers; t_grid / X / modes: out_t / out_x / out_mode of the solve.
+ * Intended use: one solve, one qmgpu_mpc_feedback_batch, then per WBC tick qmgpu_policy_eval_feedback_batch with the tick's measured centroidal state (e.g. the x0
+ * output of qmgpu_frontend_batch) followed by qmgpu_wbc_solve_batch with state_desired = x_out, input_desired = u_out, mode = mode_out. */
+int qmgpu_policy_eval_feedback_batch(qmgpu_handle h, int batch, int num_nodes, const double* t_grid, const double* X, const double* uff /*[batch][N+1][30]*/,
+                                     const double* K /*[batch][N+1][30][30]*/, const int32_t* modes, const double* t_eval, const double* x_measured /*[batch][30]*/,
+                                     double* x_out /*[batch][30]*/, double* u_out /*[batch][30]*/, int32_t* mode_out /*[batch]*/);
 
 /* Initial guess of the next MPC call from the previous solution: (X, U) of the previous grid resampled (linear interpolation, end values held, as
  * upstream's LinearInterpolation) on new_grid [batch][new_nodes + 1]; x[0] of each instance is overwritten with x0 when x0 != NULL.  The results

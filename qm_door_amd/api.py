@@ -207,6 +207,16 @@ class GpuSolver:
         abi.check(self.lib, self.lib.qmgpu_policy_eval_batch(self.handle, batch, num_nodes, _ptr(t_grid), _ptr(X), _ptr(U), _ptr(modes), _ptr(t_eval),
                                                             _ptr(x_out), _ptr(u_out), _ptr(mode_out)))
 
+    def mpc_feedback(self, batch, num_nodes, X, U, K, uff, status=None):
+        """The SQP feedback policy of the last mpc() / cycle() on this solver (qmgpu_mpc_feedback_batch; upstream's LinearController with sqp.useFeedbackPolicy):
+        K [batch][N+1][30][30], uff [batch][N+1][30] with u = uff_k + K_k x; X, U are the solve's out_x / out_u; status [batch] int32 != 0 where the solve was flagged"""
+        abi.check(self.lib, self.lib.qmgpu_mpc_feedback_batch(self.handle, batch, num_nodes, _ptr(X), _ptr(U), _ptr(K), _ptr(uff), _ptr(status)))
+
+    def policy_eval_feedback(self, batch, num_nodes, t_grid, X, uff, K, modes, t_eval, x_measured, x_out, u_out, mode_out):
+        """u_out = uff(t) + K(t) x_measured (qmgpu_policy_eval_feedback_batch; LinearController::computeInput); x_out, mode_out as policy_eval()"""
+        abi.check(self.lib, self.lib.qmgpu_policy_eval_feedback_batch(self.handle, batch, num_nodes, _ptr(t_grid), _ptr(X), _ptr(uff), _ptr(K), _ptr(modes), _ptr(t_eval),
+                                                                     _ptr(x_measured), _ptr(x_out), _ptr(u_out), _ptr(mode_out)))
+
     def pack_results(self, batch, num_nodes, X, U, wbc_out, modes, packed):
         """X | U | WBC output | modes of every instance into one row of `packed` [batch][sharding.pack_len(N)] on the handle's stream (qmgpu_pack_results): the all-gather record"""
         abi.check(self.lib, self.lib.qmgpu_pack_results(self.handle, batch, num_nodes, _ptr(X), _ptr(U), _ptr(wbc_out), _ptr(modes), _ptr(packed)))

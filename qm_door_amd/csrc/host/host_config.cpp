@@ -188,6 +188,7 @@ static void loadSettings(const std::string& taskFile, const std::string& referen
   s.swing_time_scale = infoDouble(task, "swing_trajectory_config.swingTimeScale");
   s.dt = infoDouble(task, "sqp.dt");
   s.sqp_iterations = int(infoDoubleOr(task, "sqp.sqpIteration", 1));
+  s.use_feedback_policy = infoBoolOr(task, "sqp.useFeedbackPolicy", false) ? 1 : 0;   // the sqp{} block's key, not ddp.useFeedbackPolicy (task.info:41)
   s.delta_tol = infoDoubleOr(task, "sqp.deltaTol", 1e-6);
   s.cost_tol = infoDoubleOr(task, "sqp.costTol", 1e-4);
   s.g_max = infoDoubleOr(task, "sqp.g_max", 1e6);

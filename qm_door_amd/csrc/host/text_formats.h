@@ -121,6 +121,14 @@ inline double infoDoubleOr(const InfoNode& root, const std::string& path, double
   const InfoNode* n = root.find(path);
   return (n && !n->value.empty()) ? infoDouble(root, path) : dflt;
 }
+// a boolean the way boost::property_tree reads one: true / false, or 1 / 0
+inline bool infoBoolOr(const InfoNode& root, const std::string& path, bool dflt) {
+  const InfoNode* n = root.find(path);
+  if (!n || n->value.empty()) return dflt;
+  if (n->value == "true" || n->value == "1") return true;
+  if (n->value == "false" || n->value == "0") return false;
+  throw std::runtime_error("INFO: key '" + path + "' is not a boolean: " + n->value);
+}
 // ocs2::loadData::loadEigenMatrix semantics: optional "scaling", entries "(i,j) value", missing entries are zero.
 inline void infoMatrix(const InfoNode& root, const std::string& path, int rows, int cols, double* out /*row major*/) {
   const InfoNode* n = root.find(path);

@@ -15,6 +15,7 @@
 #include "../../include/qmgpu.h"
 #include "host/host_error.h"
 #include "kernels/mpc_pipeline.h"
+#include "kernels/feedback_kernel.h"
 #include "kernels/wbc_kernel.h"
 #include "kernels/frontend_kernel.h"
 #include "mpc32.h"
@@ -67,7 +68,7 @@ struct qmgpu_context {
   long callCount = 0;   // calls recorded since timing was enabled
   hipEvent_t* ev = nullptr;
   double lastMs[5] = {0, 0, 0, 0, 0};
-  int lastBatch = 0, lastN = 0;
+  int lastBatch = 0, lastN = 0, lastAlgorithm = QMGPU_ALG_SQP;   // shape and solver of the last solve: what qmgpu_mpc_feedback_batch / qmgpu_debug_get_lq may read
 
   std::vector<std::pair<void*, size_t>> scratch;   // buffers every call rewrites (qmgpu_debug_poison fills them with NaN)
   template <class T> T* alloc(size_t count, bool isScratch = true) {
@@ -330,7 +331,7 @@ static void enqueueMpc(qmgpu_handle h, const qmgpu_mpc_args* a) {
     enqueueMpcKernels(h->stream, h->m, io, iterations, h->debugLq, ev);
   }
   HIP_CHECK(hipGetLastError());
-  h->lastBatch = a->batch; h->lastN = a->num_nodes;
+  h->lastBatch = a->batch; h->lastN = a->num_nodes; h->lastAlgorithm = a->algorithm;
 }
 
 static void enqueueWbc(qmgpu_handle h, const qmgpu_wbc_args* w, hipStream_t stream) {
@@ -380,6 +381,31 @@ int qmgpu_policy_eval_batch(qmgpu_handle h, int batch, int num_nodes, const doub
   if (!h || !t_grid || !X || !U || !modes || !t_eval || !x_out || !u_out || !mode_out || batch < 1 || num_nodes < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad arguments");
   return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device);
     QM_LAUNCH(policy_eval_kernel, batch, 64, h->stream, batch, num_nodes, t_grid, X, U, modes, t_eval, x_out, u_out, mode_out);
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
+int qmgpu_mpc_feedback_batch(qmgpu_handle h, int batch, int num_nodes, const double* X, const double* U, double* K, double* uff, int32_t* status) {
+  if (!h || !X || !U || !K || !uff || batch < 1 || num_nodes < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad feedback arguments");
+  if (h->dtype != QMGPU_F64) return setError(QMGPU_ERR_INVALID_ARGUMENT, "the feedback policy exists for QMGPU_F64 handles only");
+  if (h->lastBatch < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "qmgpu_mpc_feedback_batch needs a solve on this handle first");
+  if (h->lastAlgorithm != QMGPU_ALG_SQP) return setError(QMGPU_ERR_INVALID_ARGUMENT, "the feedback policy exists for QMGPU_ALG_SQP solves only");
+  if (batch != h->lastBatch || num_nodes != h->lastN) return setError(QMGPU_ERR_INVALID_ARGUMENT, "batch / num_nodes differ from the last solve on this handle");
+  // reads the stage records, the Riccati gains and the sweep's status of the last solve (nothing a WBC pending on the overlap stream touches) plus X, U
+  return guarded([&]() { DeviceGuard onDevice(h->device);
+    static_assert(sizeof(int) == sizeof(int32_t), "status words");
+    FeedbackArgs fa{batch, num_nodes, h->m.dStages, h->m.dGains, h->m.dInstStats, X, U, K, uff, status};
+    QM_LAUNCH(feedback_gain_kernel, batch * (num_nodes + 1), 64, h->stream, fa);
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
+int qmgpu_policy_eval_feedback_batch(qmgpu_handle h, int batch, int num_nodes, const double* t_grid, const double* X, const double* uff, const double* K, const int32_t* modes,
+                                     const double* t_eval, const double* x_measured, double* x_out, double* u_out, int32_t* mode_out) {
+  if (!h || !t_grid || !X || !uff || !K || !modes || !t_eval || !x_measured || !x_out || !u_out || !mode_out || batch < 1 || num_nodes < 1)
+    return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  return guarded([&]() { DeviceGuard onDevice(h->device);
+    QM_LAUNCH(policy_feedback_kernel, batch, 64, h->stream, batch, num_nodes, t_grid, X, uff, K, modes, t_eval, x_measured, x_out, u_out, mode_out);
     HIP_CHECK(hipGetLastError());
   });
 }

@@ -140,7 +140,11 @@ def load_library(path=None):
     lib.qmgpu_frontend_batch.argtypes = [C.c_void_p, C.POINTER(FrontendArgs)]
     lib.qmgpu_tile_gait.argtypes = [C.POINTER(Gait), d, d, d, C.POINTER(i32), C.POINTER(d), C.POINTER(i32)]
     lib.qmgpu_time_grid_with_events.argtypes = [d, d, d, i32, C.POINTER(d), i32, C.POINTER(i32), C.POINTER(d)]
+    lib.qmgpu_switch_gait.argtypes = [C.POINTER(Gait), i32, d, d, d, d, C.POINTER(i32), C.POINTER(d), C.POINTER(i32)]
     lib.qmgpu_create.argtypes = [C.POINTER(Problem), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.qmgpu_create_ex.argtypes = [C.POINTER(Problem), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.qmgpu_update_settings.argtypes = [C.c_void_p, C.POINTER(Settings)]
+    lib.qmgpu_gait_schedule_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(Gait), C.c_int] + [C.c_void_p] * 9
     lib.qmgpu_destroy.argtypes = [C.c_void_p]
     lib.qmgpu_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     lib.qmgpu_synchronize.argtypes = [C.c_void_p]

@@ -53,3 +53,10 @@ int guarded(F&& f) {
 }
 
 }  // namespace qmhost
+
+// a HIP runtime call that must succeed: HipFailure (QMGPU_ERR_HIP) with the failing expression and HIP's own message.  For translation units that see the HIP runtime.
+#define HIP_CHECK(expr)                                                                                               \
+  do {                                                                                                                \
+    hipError_t e_ = (expr);                                                                                           \
+    if (e_ != hipSuccess) throw qmhost::HipFailure(std::string(#expr) + " failed: " + hipGetErrorString(e_));         \
+  } while (0)

@@ -18,12 +18,12 @@ struct Mpc32;
 // (count, element size, is scratch) -> device memory owned by the handle
 using RawAlloc = std::function<void*(size_t, size_t, bool)>;
 
-// nullptr on failure (HIP error); the object itself is host memory, its device buffers belong to the handle's allocation list
+// Failures leave as the exceptions of host/host_error.h.  The object itself is host memory (delete it); its device buffers come from `alloc`, the handle's allocator.
 Mpc32* create(const qmgpu_problem& problem, int maxBatch, int maxNodes, hipStream_t stream, const RawAlloc& alloc);
 void destroy(Mpc32* p);
-bool updateProblem(Mpc32* p, const qmgpu_problem& problem, hipStream_t stream);
+void updateProblem(Mpc32* p, const qmgpu_problem& problem, hipStream_t stream);
 // One MPC call in fp32: the caller's fp64 device arrays are converted to fp32 staging, the kernel chain of kernels/mpc_pipeline.h
-// runs in fp32, the results are converted back into the caller's fp64 arrays.  ev: optional timing events (qmgpu_api.hip).
-bool enqueue(Mpc32* p, hipStream_t stream, const qmgpu_mpc_args* a, double dt, int iterations, int ddpTrials, hipEvent_t* ev);
+// runs in fp32, the results are converted back into the caller's fp64 arrays.  ev: the call's timing events or null.
+void enqueue(Mpc32* p, hipStream_t stream, const qmgpu_mpc_args* a, const qmgpu_settings& settings, hipEvent_t* ev, const RawAlloc& alloc);
 
 }  // namespace qmk32

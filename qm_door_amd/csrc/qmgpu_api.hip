@@ -2,13 +2,15 @@
 //
 // One handle owns one HIP stream and all scratch in HBM, sized for (max_batch, max_nodes) at create time and laid out
 // horizon-stacked (layout.h).  A call enqueues, on that stream:
-//     mpc_init -> lq_node (batch*(N+1) wavefronts) -> riccati (batch wavefronts) -> linesearch (batch workgroups)
+//     mpc_init -> ad_node -> lq_node (batch*(N+1) wavefronts) -> riccati (batch wavefronts) -> linesearch (batch workgroups)     [kernels/mpc_pipeline.h: enqueueMpcSolve]
 //     -> policy_eval -> wbc (batch workgroups)
 // with no host synchronisation in between; the caller synchronises when it needs the results.
 // There is no CPU fallback: without a HIP device qmgpu_create returns QMGPU_ERR_NO_DEVICE.
+// Every entry point that takes a handle runs through onHandle; what a handle holds is released by ~qmgpu_context and nowhere else.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -23,20 +25,14 @@
 using namespace qmhost;
 using namespace qmk;
 
-#define HIP_CHECK(expr)                                                                                       \
-  do {                                                                                                        \
-    hipError_t e_ = (expr);                                                                                   \
-    if (e_ != hipSuccess) throw HipFailure(std::string(#expr) + " failed: " + hipGetErrorString(e_));         \
-  } while (0)
-
 // Every entry point runs on the device its handle was created for and leaves the caller's current device as it found it (a
-// process may hold handles on several GPUs).
+// process may hold handles on several GPUs).  mayThrow = false for destructors: a device that cannot be selected is then left alone.
 struct DeviceGuard {
   int prev = -1;
-  explicit DeviceGuard(int device) {
+  explicit DeviceGuard(int device, bool mayThrow = true) {
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device) HIP_CHECK(hipSetDevice(device));
-    else prev = -1;
+    if (prev == device) { prev = -1; return; }
+    try { HIP_CHECK(hipSetDevice(device)); } catch (...) { prev = -1; if (mayThrow) throw; }
   }
   ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
   DeviceGuard(const DeviceGuard&) = delete;
@@ -61,12 +57,12 @@ struct qmgpu_context {
   qmgpu_gait* dGaits = nullptr;   // gait templates of the last qmgpu_gait_schedule_batch call
   std::vector<void*> allocations;
   bool timing = false, debugLq = false;
-  // HIP-event ring: one set of 7 events per call while timing is enabled, read back without a per-call sync
+  // HIP-event ring: one set of TIMING_EVENTS events (kernels/mpc_pipeline.h) per call while timing is enabled, read back without a per-call sync
   static constexpr int kRing = 256;
-  hipEvent_t ring[kRing][7];
+  hipEvent_t ring[kRing][TIMING_EVENTS] = {};
   int ringKind[kRing];  // bit0: mpc recorded, bit1: wbc recorded
   long callCount = 0;   // calls recorded since timing was enabled
-  hipEvent_t* ev = nullptr;
+  hipEvent_t* ev = ring[0];
   double lastMs[5] = {0, 0, 0, 0, 0};
   int lastBatch = 0, lastN = 0, lastAlgorithm = QMGPU_ALG_SQP;   // shape and solver of the last solve: what qmgpu_mpc_feedback_batch / qmgpu_debug_get_lq may read
 
@@ -78,7 +74,29 @@ struct qmgpu_context {
     if (isScratch) scratch.emplace_back(p, count * sizeof(T));
     return static_cast<T*>(p);
   }
+  // the same for the buffers the MPC paths of either precision size themselves (allocateMpcBuffers, ensureDdpBuffers, qmk32::create)
+  const qmk32::RawAlloc rawAlloc = [this](size_t count, size_t elem, bool isScratch) { return static_cast<void*>(alloc<char>(count * elem, isScratch)); };
+
+  qmgpu_context() = default;
+  qmgpu_context(const qmgpu_context&) = delete;
+  // releases whatever has been created so far (a create that failed half way included), after the work in flight on the handle's streams
+  ~qmgpu_context() {
+    DeviceGuard onDevice(device, false);
+    if (ownStream) (void)hipStreamSynchronize(stream);
+    if (wbcStream) { (void)hipStreamSynchronize(wbcStream); (void)hipStreamDestroy(wbcStream); }
+    for (hipEvent_t e : {evPolicy, evWbc}) if (e) (void)hipEventDestroy(e);
+    for (void* p : allocations) (void)hipFree(p);
+    for (auto& set : ring) for (auto& e : set) if (e) (void)hipEventDestroy(e);
+    if (ownStream) (void)hipStreamDestroy(ownStream);
+    qmk32::destroy(m32);
+  }
 };
+
+// The preamble of every entry point that takes a handle: null test, exceptions -> status (guarded), the handle's device current while body runs.
+template <class F> static int onHandle(qmgpu_handle h, F&& body) {
+  if (!h) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null handle");
+  return guarded([&]() { DeviceGuard onDevice(h->device); body(); });
+}
 
 static void checkTopology(const qmgpu_model& m) {
   bool ok = m.parent[0] == -1;
@@ -102,23 +120,19 @@ int qmgpu_create(const qmgpu_problem* problem, int device, int max_batch, int ma
 int qmgpu_create_ex(const qmgpu_problem* problem, int device, int max_batch, int max_nodes, int dtype, qmgpu_handle* out) {
   if (!problem || !out || max_batch < 1 || max_nodes < 1 || (dtype != QMGPU_F64 && dtype != QMGPU_F32)) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad arguments to qmgpu_create");
   *out = nullptr;
-  qmgpu_context* ctx = nullptr;
-  const int st = guarded([&]() {
+  return guarded([&]() {
     checkTopology(problem->model);
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) throw NoDevice("no HIP device visible; qm_door_amd has no CPU execution path");
     if (device < 0 || device >= count) throw NoDevice("HIP device index out of range");
     DeviceGuard onDevice(device);
-    ctx = new qmgpu_context();
-    for (auto& set : ctx->ring) for (auto& e : set) e = nullptr;
+    auto ctx = std::make_unique<qmgpu_context>();   // nothing of a failed create survives: device memory, events, stream
     ctx->device = device; ctx->maxBatch = max_batch; ctx->maxNodes = max_nodes; ctx->hostProblem = *problem; ctx->dtype = dtype;
     HIP_CHECK(hipStreamCreate(&ctx->ownStream));
     ctx->stream = ctx->ownStream;
-    const size_t B = size_t(max_batch), N1 = size_t(max_nodes) + 1, N = size_t(max_nodes);
-    qmgpu_context* const owner = ctx;   // by value: the fp32 path keeps this allocator for buffers it creates on first use
-    auto rawAlloc = [owner](size_t count, size_t elem, bool scratch) { return static_cast<void*>(owner->alloc<char>(count * elem, scratch)); };
+    const size_t B = size_t(max_batch), N = size_t(max_nodes);
     // the fp32 handle keeps the fp64 model / settings / R' (the WBC and the front end read them) but not the fp64 MPC scratch
-    if (dtype == QMGPU_F64) allocateMpcBuffers(ctx->m, B, N, rawAlloc);
+    if (dtype == QMGPU_F64) allocateMpcBuffers(ctx->m, B, N, ctx->rawAlloc);
     else { ctx->m.dP = ctx->alloc<qmgpu_problem>(1, false); ctx->m.dRw = ctx->alloc<double>(qmk::QM_RW_DOUBLES, false); ctx->m.dZeros = ctx->alloc<double>(64, false); }
     ctx->dPolX = ctx->alloc<double>(B * 30);
     ctx->dPolU = ctx->alloc<double>(B * 30);
@@ -126,48 +140,18 @@ int qmgpu_create_ex(const qmgpu_problem* problem, int device, int max_batch, int
     HIP_CHECK(hipMemcpy(ctx->m.dP, problem, sizeof(qmgpu_problem), hipMemcpyHostToDevice));
     HIP_CHECK(hipMemsetAsync(ctx->m.dZeros, 0, 64 * sizeof(double), ctx->stream));
     for (auto& set : ctx->ring) for (auto& e : set) HIP_CHECK(hipEventCreate(&e));
-    ctx->ev = ctx->ring[0];
     HIP_CHECK(QM_ALLOW_DYNAMIC_LDS(wbc_kernel, WBC_LDS_BYTES));
     HIP_CHECK(prepareMpcKernels());
     QM_LAUNCH(input_weight_kernel, 1, 64, ctx->stream, ctx->m.dP, ctx->m.dZeros, ctx->m.dRw);
     HIP_CHECK(hipGetLastError());
-    if (dtype == QMGPU_F32) {
-      ctx->m32 = qmk32::create(*problem, max_batch, max_nodes, ctx->stream, rawAlloc);
-      if (!ctx->m32) throw HipFailure("fp32 MPC path could not be created");
-    }
+    if (dtype == QMGPU_F32) ctx->m32 = qmk32::create(*problem, max_batch, max_nodes, ctx->stream, ctx->rawAlloc);
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    *out = ctx.release();
   });
-  if (st != QMGPU_OK) {
-    if (ctx) {   // nothing of a failed create survives: device memory, events, stream
-      int prev = -1;
-      const bool sw = hipGetDevice(&prev) == hipSuccess && prev != ctx->device && hipSetDevice(ctx->device) == hipSuccess;
-      for (void* p : ctx->allocations) hipFree(p);
-      for (auto& set : ctx->ring) for (auto& e : set) if (e) hipEventDestroy(e);
-      if (ctx->ownStream) hipStreamDestroy(ctx->ownStream);
-      if (sw) hipSetDevice(prev);
-      qmk32::destroy(ctx->m32);
-      delete ctx;
-    }
-    return st;
-  }
-  *out = ctx;
-  return QMGPU_OK;
 }
 
 int qmgpu_destroy(qmgpu_handle h) {
-  if (!h) return QMGPU_OK;
-  int prev = -1;
-  const bool sw = hipGetDevice(&prev) == hipSuccess && prev != h->device && hipSetDevice(h->device) == hipSuccess;
-  hipStreamSynchronize(h->stream);
-  if (h->wbcStream) { hipStreamSynchronize(h->wbcStream); hipStreamDestroy(h->wbcStream); }
-  if (h->evPolicy) hipEventDestroy(h->evPolicy);
-  if (h->evWbc) hipEventDestroy(h->evWbc);
-  for (void* p : h->allocations) hipFree(p);
-  for (auto& set : h->ring) for (auto& e : set) if (e) hipEventDestroy(e);
-  if (h->ownStream) hipStreamDestroy(h->ownStream);
-  if (sw) hipSetDevice(prev);
-  qmk32::destroy(h->m32);
-  delete h;
+  delete h;   // (null: nothing to do)
   return QMGPU_OK;
 }
 
@@ -177,19 +161,16 @@ static void joinWbc(qmgpu_handle h) {
 }
 
 int qmgpu_set_stream(qmgpu_handle h, void* hip_stream) {
-  if (!h) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null handle");
   // the NEW stream is the one that has to wait for a WBC still pending on the overlap stream: everything enqueued from here on goes there
-  return guarded([&]() { DeviceGuard onDevice(h->device); h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->ownStream; joinWbc(h); });
+  return onHandle(h, [&]() { h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->ownStream; joinWbc(h); });
 }
 
 int qmgpu_synchronize(qmgpu_handle h) {
-  if (!h) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null handle");
-  return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device); joinWbc(h); HIP_CHECK(hipStreamSynchronize(h->stream)); });
+  return onHandle(h, [&]() { joinWbc(h); HIP_CHECK(hipStreamSynchronize(h->stream)); });
 }
 
 int qmgpu_set_overlap(qmgpu_handle h, int enable) {
-  if (!h) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null handle");
-  return guarded([&]() { DeviceGuard onDevice(h->device);
+  return onHandle(h, [&]() {
     joinWbc(h);
     if (enable) {   // (each resource on its own: a call that failed half way is repeated without leaking what it had created)
       // a HIGH-PRIORITY stream: the runtime spreads streams of one priority over a few hardware queues round robin, and two streams that land on the same queue run
@@ -208,34 +189,29 @@ int qmgpu_set_overlap(qmgpu_handle h, int enable) {
 }
 
 int qmgpu_join_wbc(qmgpu_handle h) {
-  if (!h) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null handle");
-  return guarded([&]() { DeviceGuard onDevice(h->device); joinWbc(h); });
+  return onHandle(h, [&]() { joinWbc(h); });
 }
 
 int qmgpu_update_settings(qmgpu_handle h, const qmgpu_settings* settings) {
-  if (!h || !settings) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null argument");
-  return guarded([&]() {
-    DeviceGuard onDevice(h->device);
+  if (!settings) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null argument");
+  return onHandle(h, [&]() {
     joinWbc(h);
     HIP_CHECK(hipStreamSynchronize(h->stream));   // kernels in flight (a WBC on the overlap stream included) still read the old values through dP
     h->hostProblem.settings = *settings;
     HIP_CHECK(hipMemcpy(&h->m.dP->settings, &h->hostProblem.settings, sizeof(qmgpu_settings), hipMemcpyHostToDevice));
     QM_LAUNCH(input_weight_kernel, 1, 64, h->stream, h->m.dP, h->m.dZeros, h->m.dRw);
     HIP_CHECK(hipGetLastError());
-    if (h->m32 && !qmk32::updateProblem(h->m32, h->hostProblem, h->stream)) throw HipFailure("fp32 settings update failed");
+    if (h->m32) qmk32::updateProblem(h->m32, h->hostProblem, h->stream);
   });
 }
 
 int qmgpu_get_input_weight(qmgpu_handle h, double* R_host) {
-  if (!h || !R_host) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null argument");
-  return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device); HIP_CHECK(hipStreamSynchronize(h->stream)); HIP_CHECK(hipMemcpy(R_host, h->m.dRw, 900 * sizeof(double), hipMemcpyDeviceToHost)); });
+  if (!R_host) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null argument");
+  return onHandle(h, [&]() { HIP_CHECK(hipStreamSynchronize(h->stream)); HIP_CHECK(hipMemcpy(R_host, h->m.dRw, 900 * sizeof(double), hipMemcpyDeviceToHost)); });
 }
 
 int qmgpu_enable_timing(qmgpu_handle h, int enable) {
-  if (!h) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null handle");
-  h->timing = enable != 0;
-  h->callCount = 0;
-  return QMGPU_OK;
+  return onHandle(h, [&]() { h->timing = enable != 0; h->callCount = 0; });
 }
 
 // fills one CU's worth of LDS with NaN; launched with many more workgroups than CUs so that every CU gets some
@@ -282,8 +258,7 @@ int qmgpu_debug_ad_wg_clocks(unsigned long long* out64, int count) {
 #endif
 
 int qmgpu_debug_poison(qmgpu_handle h) {
-  if (!h) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null handle");
-  return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device);
+  return onHandle(h, [&]() {
     joinWbc(h);      // (a pending WBC still reads the policy buffers, which are scratch)
     for (auto& sc : h->scratch) HIP_CHECK(hipMemsetAsync(sc.first, 0xFF, sc.second, h->stream));
     constexpr int kDoubles = 160 * 1024 / 8;
@@ -294,8 +269,7 @@ int qmgpu_debug_poison(qmgpu_handle h) {
 }
 
 int qmgpu_enable_debug(qmgpu_handle h, int enable) {
-  if (!h) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null handle");
-  return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device);
+  return onHandle(h, [&]() {
     if (enable && h->dtype != QMGPU_F64) throw std::invalid_argument("the per-node LQ dump exists in the fp64 path only");
     if (enable && !h->m.dDebug) h->m.dDebug = h->alloc<double>(size_t(h->maxBatch) * (h->maxNodes + 1) * DBG_DOUBLES);
     h->debugLq = enable != 0;
@@ -303,7 +277,7 @@ int qmgpu_enable_debug(qmgpu_handle h, int enable) {
 }
 
 static void checkMpcArgs(qmgpu_handle h, const qmgpu_mpc_args* a) {
-  if (!h || !a) throw std::invalid_argument("null argument");
+  if (!a) throw std::invalid_argument("null argument");
   if (a->batch < 1 || a->num_nodes < 1 || a->num_target_knots < 1) throw std::invalid_argument("batch, num_nodes and num_target_knots must be positive");
   if (a->batch > h->maxBatch || a->num_nodes > h->maxNodes) throw CapacityError("batch / num_nodes exceed the capacity given to qmgpu_create");
   if (h->dtype == QMGPU_F32 && a->num_target_knots > QMGPU_F32_MAX_TARGET_KNOTS) throw CapacityError("an fp32 handle stages at most QMGPU_F32_MAX_TARGET_KNOTS target knots per instance");
@@ -313,24 +287,14 @@ static void checkMpcArgs(qmgpu_handle h, const qmgpu_mpc_args* a) {
 }
 
 static void enqueueMpc(qmgpu_handle h, const qmgpu_mpc_args* a) {
-  const int iterations = h->hostProblem.settings.sqp_iterations > 1 ? h->hostProblem.settings.sqp_iterations : 1;
+  const qmgpu_settings& settings = h->hostProblem.settings;
   hipEvent_t* ev = h->timing ? h->ev : nullptr;
-  if (a->algorithm != QMGPU_ALG_SQP && a->algorithm != QMGPU_ALG_DDP) throw std::invalid_argument("unknown qmgpu_mpc_args::algorithm");
-  const int trials = ddpTrialCount(h->hostProblem.settings.ddp_min_step, h->hostProblem.settings.ddp_max_step);
   if (h->dtype == QMGPU_F32) {
-    if (!qmk32::enqueue(h->m32, h->stream, a, h->hostProblem.settings.dt, iterations, trials, ev)) throw HipFailure("fp32 MPC launch failed");
-  } else if (a->algorithm == QMGPU_ALG_DDP) {
-    ensureDdpBuffers(h->m, size_t(h->maxBatch), size_t(h->maxNodes), [&](size_t count, size_t elem, bool scratch) { return static_cast<void*>(h->alloc<char>(count * elem, scratch)); });
-    const MpcIo io{a->batch, a->num_nodes, a->num_target_knots, a->line_search, h->hostProblem.settings.dt, a->t0, a->time_grid, a->sched_event_times, a->x0, a->target_times,
-                   a->target_states, a->sched_num_events, a->sched_event_times, a->sched_modes, a->warm_x, a->warm_u, a->out_t, a->out_x, a->out_u, a->out_mode, a->out_stats, a->ee_contact_ref,
-                   a->algorithm};
-    enqueueDdpKernels(h->stream, h->m, io, trials, ev);
+    qmk32::enqueue(h->m32, h->stream, a, settings, ev, h->rawAlloc);
   } else {
-    const MpcIo io{a->batch, a->num_nodes, a->num_target_knots, a->line_search, h->hostProblem.settings.dt, a->t0, a->time_grid, a->sched_event_times, a->x0, a->target_times,
-                   a->target_states, a->sched_num_events, a->sched_event_times, a->sched_modes, a->warm_x, a->warm_u, a->out_t, a->out_x, a->out_u, a->out_mode, a->out_stats, a->ee_contact_ref, a->algorithm};
-    enqueueMpcKernels(h->stream, h->m, io, iterations, h->debugLq, ev);
+    const MpcIo io = makeMpcIo(*a, settings.dt, MpcStaging{}, [](const double* src, double*, size_t) { return src; }, a->out_t, a->out_x, a->out_u, a->out_stats);
+    enqueueMpcSolve(h->stream, h->m, io, settings, h->debugLq, ev, h->rawAlloc);
   }
-  HIP_CHECK(hipGetLastError());
   h->lastBatch = a->batch; h->lastN = a->num_nodes; h->lastAlgorithm = a->algorithm;
 }
 
@@ -353,46 +317,41 @@ static void finishTiming(qmgpu_handle h, bool mpc, bool wbc) {
   h->ringKind[h->callCount % qmgpu_context::kRing] = (mpc ? 1 : 0) | (wbc ? 2 : 0);
   ++h->callCount;
 }
-// elapsed times of one recorded call: [ad_node, lq_node, riccati, linesearch, wbc, whole]  (events: 0 start, 6 after ad, 1 after lq, 2, 3, 4/5 wbc)
+// elapsed times of one recorded call: [ad_node, lq_node, riccati, linesearch, wbc, whole]
 static void readTiming(qmgpu_handle h, long call, double* ms6) {
   hipEvent_t* ev = h->ring[call % qmgpu_context::kRing];
   const int kind = h->ringKind[call % qmgpu_context::kRing];
   const bool mpc = kind & 1, wbc = kind & 2;
-  HIP_CHECK(hipEventSynchronize(ev[wbc ? 5 : 3]));
-  float ms = 0.f;
+  const TimingEvent first = mpc ? EV_START : EV_WBC_START, last = wbc ? EV_WBC_END : EV_LINE_SEARCH;
+  HIP_CHECK(hipEventSynchronize(ev[last]));
+  auto elapsed = [&](TimingEvent from, TimingEvent to) { float ms = 0.f; HIP_CHECK(hipEventElapsedTime(&ms, ev[from], ev[to])); return double(ms); };
   for (int i = 0; i < 6; ++i) ms6[i] = 0.0;
-  if (mpc) {
-    HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[6])); ms6[0] = ms;
-    HIP_CHECK(hipEventElapsedTime(&ms, ev[6], ev[1])); ms6[1] = ms;
-    HIP_CHECK(hipEventElapsedTime(&ms, ev[1], ev[2])); ms6[2] = ms;
-    HIP_CHECK(hipEventElapsedTime(&ms, ev[2], ev[3])); ms6[3] = ms;
-  }
-  if (wbc) { HIP_CHECK(hipEventElapsedTime(&ms, ev[4], ev[5])); ms6[4] = ms; }
-  HIP_CHECK(hipEventElapsedTime(&ms, ev[mpc ? 0 : 4], ev[wbc ? 5 : 3]));
-  ms6[5] = ms;
+  if (mpc) for (int k = EV_AD_NODE; k <= EV_LINE_SEARCH; ++k) ms6[k - EV_AD_NODE] = elapsed(TimingEvent(k - 1), TimingEvent(k));   // each kernel: from the event before it
+  if (wbc) ms6[4] = elapsed(EV_WBC_START, EV_WBC_END);
+  ms6[5] = elapsed(first, last);
 }
 
 int qmgpu_mpc_solve_batch(qmgpu_handle h, const qmgpu_mpc_args* args) {
-  return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device); checkMpcArgs(h, args); beginTiming(h); enqueueMpc(h, args); finishTiming(h, true, false); });
+  return onHandle(h, [&]() { checkMpcArgs(h, args); beginTiming(h); enqueueMpc(h, args); finishTiming(h, true, false); });
 }
 
 int qmgpu_policy_eval_batch(qmgpu_handle h, int batch, int num_nodes, const double* t_grid, const double* X, const double* U, const int32_t* modes, const double* t_eval,
                             double* x_out, double* u_out, int32_t* mode_out) {
-  if (!h || !t_grid || !X || !U || !modes || !t_eval || !x_out || !u_out || !mode_out || batch < 1 || num_nodes < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad arguments");
-  return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device);
+  if (!t_grid || !X || !U || !modes || !t_eval || !x_out || !u_out || !mode_out || batch < 1 || num_nodes < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  return onHandle(h, [&]() {
     QM_LAUNCH(policy_eval_kernel, batch, 64, h->stream, batch, num_nodes, t_grid, X, U, modes, t_eval, x_out, u_out, mode_out);
     HIP_CHECK(hipGetLastError());
   });
 }
 
 int qmgpu_mpc_feedback_batch(qmgpu_handle h, int batch, int num_nodes, const double* X, const double* U, double* K, double* uff, int32_t* status) {
-  if (!h || !X || !U || !K || !uff || batch < 1 || num_nodes < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad feedback arguments");
-  if (h->dtype != QMGPU_F64) return setError(QMGPU_ERR_INVALID_ARGUMENT, "the feedback policy exists for QMGPU_F64 handles only");
-  if (h->lastBatch < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "qmgpu_mpc_feedback_batch needs a solve on this handle first");
-  if (h->lastAlgorithm != QMGPU_ALG_SQP) return setError(QMGPU_ERR_INVALID_ARGUMENT, "the feedback policy exists for QMGPU_ALG_SQP solves only");
-  if (batch != h->lastBatch || num_nodes != h->lastN) return setError(QMGPU_ERR_INVALID_ARGUMENT, "batch / num_nodes differ from the last solve on this handle");
+  if (!X || !U || !K || !uff || batch < 1 || num_nodes < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad feedback arguments");
   // reads the stage records, the Riccati gains and the sweep's status of the last solve (nothing a WBC pending on the overlap stream touches) plus X, U
-  return guarded([&]() { DeviceGuard onDevice(h->device);
+  return onHandle(h, [&]() {
+    if (h->dtype != QMGPU_F64) throw std::invalid_argument("the feedback policy exists for QMGPU_F64 handles only");
+    if (h->lastBatch < 1) throw std::invalid_argument("qmgpu_mpc_feedback_batch needs a solve on this handle first");
+    if (h->lastAlgorithm != QMGPU_ALG_SQP) throw std::invalid_argument("the feedback policy exists for QMGPU_ALG_SQP solves only");
+    if (batch != h->lastBatch || num_nodes != h->lastN) throw std::invalid_argument("batch / num_nodes differ from the last solve on this handle");
     static_assert(sizeof(int) == sizeof(int32_t), "status words");
     FeedbackArgs fa{batch, num_nodes, h->m.dStages, h->m.dGains, h->m.dInstStats, X, U, K, uff, status};
     QM_LAUNCH(feedback_gain_kernel, batch * (num_nodes + 1), 64, h->stream, fa);
@@ -402,18 +361,18 @@ int qmgpu_mpc_feedback_batch(qmgpu_handle h, int batch, int num_nodes, const dou
 
 int qmgpu_policy_eval_feedback_batch(qmgpu_handle h, int batch, int num_nodes, const double* t_grid, const double* X, const double* uff, const double* K, const int32_t* modes,
                                      const double* t_eval, const double* x_measured, double* x_out, double* u_out, int32_t* mode_out) {
-  if (!h || !t_grid || !X || !uff || !K || !modes || !t_eval || !x_measured || !x_out || !u_out || !mode_out || batch < 1 || num_nodes < 1)
+  if (!t_grid || !X || !uff || !K || !modes || !t_eval || !x_measured || !x_out || !u_out || !mode_out || batch < 1 || num_nodes < 1)
     return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad arguments");
-  return guarded([&]() { DeviceGuard onDevice(h->device);
+  return onHandle(h, [&]() {
     QM_LAUNCH(policy_feedback_kernel, batch, 64, h->stream, batch, num_nodes, t_grid, X, uff, K, modes, t_eval, x_measured, x_out, u_out, mode_out);
     HIP_CHECK(hipGetLastError());
   });
 }
 
 int qmgpu_frontend_batch(qmgpu_handle h, const qmgpu_frontend_args* a) {
-  if (!h || !a || a->batch < 1 || !a->rbd_measured || !a->time || !a->command_kind || !a->command || !a->last_ee_target || !a->x0 || !a->target_times || !a->target_states)
+  if (!a || a->batch < 1 || !a->rbd_measured || !a->time || !a->command_kind || !a->command || !a->last_ee_target || !a->x0 || !a->target_times || !a->target_states)
     return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad front-end arguments");
-  return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device);
+  return onHandle(h, [&]() {
     FrontendArgs fa{h->m.dP, *a};
     QM_LAUNCH(frontend_kernel, (a->batch + 63) / 64, 64, h->stream, fa);
     HIP_CHECK(hipGetLastError());
@@ -422,10 +381,9 @@ int qmgpu_frontend_batch(qmgpu_handle h, const qmgpu_frontend_args* a) {
 
 int qmgpu_gait_schedule_batch(qmgpu_handle h, int batch, const qmgpu_gait* templates, int num_templates, const int32_t* gait_index, const int32_t* prev_mode,
                               const double* t_phase0, const double* t_begin, const double* t_end, int32_t* sched_num_events, double* sched_event_times, int32_t* sched_modes, int32_t* status) {
-  if (!h || batch < 1 || !templates || num_templates < 1 || num_templates > 64 || !gait_index || !t_phase0 || !t_begin || !t_end || !sched_num_events || !sched_event_times || !sched_modes)
+  if (batch < 1 || !templates || num_templates < 1 || num_templates > 64 || !gait_index || !t_phase0 || !t_begin || !t_end || !sched_num_events || !sched_event_times || !sched_modes)
     return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad gait schedule arguments");
-  return guarded([&]() {
-    DeviceGuard onDevice(h->device);
+  return onHandle(h, [&]() {
     if (!h->dGaits) h->dGaits = h->alloc<qmgpu_gait>(64, false);
     HIP_CHECK(hipMemcpyAsync(h->dGaits, templates, sizeof(qmgpu_gait) * num_templates, hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(hipStreamSynchronize(h->stream));   // `templates` is the caller's (pageable) host memory: nothing is retained after return
@@ -436,31 +394,30 @@ int qmgpu_gait_schedule_batch(qmgpu_handle h, int batch, const qmgpu_gait* templ
 }
 
 int qmgpu_wbc_solve_batch(qmgpu_handle h, const qmgpu_wbc_args* args) {
-  if (!h) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null handle");
-  return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device);
+  return onHandle(h, [&]() {
     joinWbc(h);
     beginTiming(h);
-    if (h->timing) HIP_CHECK(hipEventRecord(h->ev[4], h->stream));
+    if (h->timing) HIP_CHECK(hipEventRecord(h->ev[EV_WBC_START], h->stream));
     enqueueWbc(h, args, h->stream);
-    if (h->timing) HIP_CHECK(hipEventRecord(h->ev[5], h->stream));
+    if (h->timing) HIP_CHECK(hipEventRecord(h->ev[EV_WBC_END], h->stream));
     finishTiming(h, false, true);
   });
 }
 
 int qmgpu_warm_start_batch(qmgpu_handle h, int batch, int prev_nodes, const double* prev_grid, const double* prev_X, const double* prev_U, int new_nodes,
                            const double* new_grid, const double* x0, double* warm_x, double* warm_u) {
-  if (!h || !prev_grid || !prev_X || !prev_U || !new_grid || !warm_x || !warm_u || batch < 1 || prev_nodes < 1 || new_nodes < 1)
+  if (!prev_grid || !prev_X || !prev_U || !new_grid || !warm_x || !warm_u || batch < 1 || prev_nodes < 1 || new_nodes < 1)
     return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad warm-start arguments");
   if (warm_x == prev_X || warm_u == prev_U) return setError(QMGPU_ERR_INVALID_ARGUMENT, "warm-start outputs must not alias the previous solution");
-  return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device);
+  return onHandle(h, [&]() {
     QM_LAUNCH(warm_start_kernel, batch, 256, h->stream, batch, prev_nodes, prev_grid, prev_X, prev_U, new_nodes, new_grid, x0, warm_x, warm_u);
     HIP_CHECK(hipGetLastError());
   });
 }
 
 int qmgpu_cycle_batch(qmgpu_handle h, const qmgpu_mpc_args* mpc, const double* t_eval, qmgpu_wbc_args* wbc) {
-  if (!h || !t_eval || !wbc) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null argument");
-  return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device);
+  if (!t_eval || !wbc) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null argument");
+  return onHandle(h, [&]() {
     checkMpcArgs(h, mpc);
     if (wbc->batch != mpc->batch) throw std::invalid_argument("MPC and WBC batch sizes differ");
     beginTiming(h);
@@ -476,9 +433,9 @@ int qmgpu_cycle_batch(qmgpu_handle h, const qmgpu_mpc_args* mpc, const double* t
       HIP_CHECK(hipStreamWaitEvent(h->wbcStream, h->evPolicy, 0));
       ws = h->wbcStream;
     }
-    if (h->timing) HIP_CHECK(hipEventRecord(h->ev[4], ws));
+    if (h->timing) HIP_CHECK(hipEventRecord(h->ev[EV_WBC_START], ws));
     enqueueWbc(h, &w, ws);
-    if (h->timing) HIP_CHECK(hipEventRecord(h->ev[5], ws));
+    if (h->timing) HIP_CHECK(hipEventRecord(h->ev[EV_WBC_END], ws));
     if (h->overlap) { HIP_CHECK(hipEventRecord(h->evWbc, ws)); h->wbcPending = true; }
     finishTiming(h, true, true);
   });
@@ -486,8 +443,7 @@ int qmgpu_cycle_batch(qmgpu_handle h, const qmgpu_mpc_args* mpc, const double* t
 
 int qmgpu_debug_get_lq(qmgpu_handle h, int instance, int node, double* A, double* B, double* b, double* Q, double* R, double* q, double* r, double* C, double* D, double* e,
                        int32_t* nc) {
-  if (!h) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null handle");
-  return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device);
+  return onHandle(h, [&]() {
     if (!h->debugLq || !h->m.dDebug) throw std::invalid_argument("call qmgpu_enable_debug(h, 1) before the solve");
     if (instance < 0 || instance >= h->lastBatch || node < 0 || node > h->lastN) throw std::invalid_argument("instance / node out of range");
     HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -504,16 +460,16 @@ int qmgpu_debug_get_lq(qmgpu_handle h, int instance, int node, double* A, double
 }
 
 int qmgpu_last_kernel_ms(qmgpu_handle h, double* ms6) {
-  if (!h || !ms6) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null argument");
-  return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device);
+  if (!ms6) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null argument");
+  return onHandle(h, [&]() {
     if (!h->timing || h->callCount == 0) throw std::invalid_argument("no timed call recorded (qmgpu_enable_timing)");
     readTiming(h, h->callCount - 1, ms6);
   });
 }
 
 int qmgpu_kernel_ms_mean(qmgpu_handle h, int last_calls, double* ms6) {
-  if (!h || !ms6 || last_calls < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad argument");
-  return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device);
+  if (!ms6 || last_calls < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad argument");
+  return onHandle(h, [&]() {
     if (!h->timing || h->callCount == 0) throw std::invalid_argument("no timed call recorded (qmgpu_enable_timing)");
     const long n = std::min<long>(std::min<long>(last_calls, h->callCount), qmgpu_context::kRing);
     double acc[6] = {0, 0, 0, 0, 0, 0};
@@ -523,16 +479,16 @@ int qmgpu_kernel_ms_mean(qmgpu_handle h, int last_calls, double* ms6) {
 }
 
 int qmgpu_pack_results(qmgpu_handle h, int batch, int num_nodes, const double* X, const double* U, const double* wbc_out, const int32_t* modes, double* packed) {
-  if (!h || !X || !U || !wbc_out || !modes || !packed || batch < 1 || num_nodes < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad arguments");
-  return guarded([&]() { DeviceGuard onDevice(h->device);
+  if (!X || !U || !wbc_out || !modes || !packed || batch < 1 || num_nodes < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  return onHandle(h, [&]() {
     QM_LAUNCH(pack_results_kernel, batch, 256, h->stream, batch, num_nodes, X, U, wbc_out, modes, packed);
     HIP_CHECK(hipGetLastError());
   });
 }
 
 int qmgpu_kernel_ms_history(qmgpu_handle h, int last_calls, double* ms6_per_call) {
-  if (!h || !ms6_per_call || last_calls < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad argument");
-  return guarded([&]() { if (!h) throw std::invalid_argument("null handle"); DeviceGuard onDevice(h->device);
+  if (!ms6_per_call || last_calls < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad argument");
+  return onHandle(h, [&]() {
     if (!h->timing || h->callCount == 0) throw std::invalid_argument("no timed call recorded (qmgpu_enable_timing)");
     if (last_calls > h->callCount || last_calls > qmgpu_context::kRing) throw std::invalid_argument("more calls asked for than the event ring holds");
     for (long c = h->callCount - last_calls, i = 0; c < h->callCount; ++c, ++i) readTiming(h, c, ms6_per_call + 6 * i);

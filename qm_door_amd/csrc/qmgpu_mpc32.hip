@@ -7,7 +7,7 @@
 // fp32 counterpart, and it always runs in fp64 on the (converted) policy of either MPC path.
 #include "mpc32.h"
 
-#include <new>
+#include <memory>
 
 #include "kernels/mpc_pipeline.h"
 
@@ -25,79 +25,53 @@ __global__ void __launch_bounds__(256) widen_kernel(const float* src, double* ds
 }
 
 struct Mpc32 {
-  int maxBatch = 0, maxNodes = 0;
-  RawAlloc alloc;   // the handle's allocator (device memory stays on the handle's list)
   MpcBuffers m;
-  // fp32 staging of one call's arguments
-  float *x0 = nullptr, *tgtT = nullptr, *tgtS = nullptr, *evT = nullptr, *warmX = nullptr, *warmU = nullptr;
-  float *outT = nullptr, *outX = nullptr, *outU = nullptr, *outStats = nullptr, *contact = nullptr;
+  MpcStaging in;   // fp32 staging of one call's arguments
+  float *outT = nullptr, *outX = nullptr, *outU = nullptr, *outStats = nullptr;
 };
 
-static bool uploadProblem(Mpc32* p, const qmgpu_problem& problem, hipStream_t stream) {
+void updateProblem(Mpc32* p, const qmgpu_problem& problem, hipStream_t stream) {
   ProblemR host;
   convert(problem, host);
-  if (hipStreamSynchronize(stream) != hipSuccess) return false;
-  if (hipMemcpy(p->m.dP, &host, sizeof(ProblemR), hipMemcpyHostToDevice) != hipSuccess) return false;
+  HIP_CHECK(hipStreamSynchronize(stream));
+  HIP_CHECK(hipMemcpy(p->m.dP, &host, sizeof(ProblemR), hipMemcpyHostToDevice));
   QM_LAUNCH(input_weight_kernel, 1, 64, stream, p->m.dP, p->m.dZeros, p->m.dRw);
-  return hipGetLastError() == hipSuccess;
+  HIP_CHECK(hipGetLastError());
 }
 
 Mpc32* create(const qmgpu_problem& problem, int maxBatch, int maxNodes, hipStream_t stream, const RawAlloc& alloc) {
-  Mpc32* p = new (std::nothrow) Mpc32();
-  if (!p) return nullptr;
-  p->maxBatch = maxBatch; p->maxNodes = maxNodes; p->alloc = alloc;
+  auto p = std::make_unique<Mpc32>();
   const size_t B = size_t(maxBatch), N = size_t(maxNodes), N1 = N + 1;
   allocateMpcBuffers(p->m, B, N, alloc);
   auto F = [&](size_t n) { return static_cast<float*>(alloc(n, sizeof(float), true)); };
-  p->x0 = F(B * 30); p->tgtT = F(B * kMaxKnots32); p->tgtS = F(B * kMaxKnots32 * QMGPU_NTARGET); p->evT = F(B * QMGPU_MAX_EVENTS);
-  p->warmX = F(B * N1 * 30); p->warmU = F(B * N * 30);
-  p->outT = F(B * N1); p->outX = F(B * N1 * 30); p->outU = F(B * N * 30); p->outStats = F(B * QMGPU_NSTATS); p->contact = F(B * kMaxKnots32 * 6);
-  if (hipMemsetAsync(p->m.dZeros, 0, 64 * sizeof(float), stream) != hipSuccess || prepareMpcKernels() != hipSuccess || !uploadProblem(p, problem, stream) ||
-      hipStreamSynchronize(stream) != hipSuccess) {
-    delete p;
-    return nullptr;
-  }
-  return p;
+  p->in.x0 = F(B * 30); p->in.targetTimes = F(B * kMaxKnots32); p->in.targetStates = F(B * kMaxKnots32 * QMGPU_NTARGET); p->in.schedTimes = F(B * QMGPU_MAX_EVENTS);
+  p->in.warmX = F(B * N1 * 30); p->in.warmU = F(B * N * 30);
+  p->outT = F(B * N1); p->outX = F(B * N1 * 30); p->outU = F(B * N * 30); p->outStats = F(B * QMGPU_NSTATS); p->in.eeContact = F(B * kMaxKnots32 * 6);
+  HIP_CHECK(hipMemsetAsync(p->m.dZeros, 0, 64 * sizeof(float), stream));
+  HIP_CHECK(prepareMpcKernels());
+  updateProblem(p.get(), problem, stream);
+  HIP_CHECK(hipStreamSynchronize(stream));
+  return p.release();
 }
 
 void destroy(Mpc32* p) { delete p; }
 
-bool updateProblem(Mpc32* p, const qmgpu_problem& problem, hipStream_t stream) { return p && uploadProblem(p, problem, stream); }
-
-bool enqueue(Mpc32* p, hipStream_t s, const qmgpu_mpc_args* a, double dtD, int iterations, int ddpTrials, hipEvent_t* ev) {
-  if (!p || a->num_target_knots > kMaxKnots32) return false;
-  const size_t B = size_t(a->batch), N = size_t(a->num_nodes), N1 = N + 1, K = size_t(a->num_target_knots);
+void enqueue(Mpc32* p, hipStream_t s, const qmgpu_mpc_args* a, const qmgpu_settings& settings, hipEvent_t* ev, const RawAlloc& alloc) {
+  if (a->num_target_knots > kMaxKnots32) throw qmhost::CapacityError("more target knots than the fp32 staging holds");
+  const size_t B = size_t(a->batch), N = size_t(a->num_nodes), N1 = N + 1;
   auto narrow = [&](const double* src, float* dst, size_t n) {
     if (!src) return static_cast<const float*>(nullptr);
     QM_LAUNCH(narrow_kernel, unsigned((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), 256, s, src, dst, n);
     return static_cast<const float*>(dst);
   };
-  MpcIo io{};
-  io.batch = a->batch; io.N = a->num_nodes; io.K = a->num_target_knots; io.lineSearch = a->line_search;
-  io.dtD = dtD; io.t0D = a->t0; io.timeGridD = a->time_grid; io.schedTimesD = a->sched_event_times;
-  io.x0 = narrow(a->x0, p->x0, B * 30);
-  io.targetTimes = narrow(a->target_times, p->tgtT, B * K);
-  io.targetStates = narrow(a->target_states, p->tgtS, B * K * QMGPU_NTARGET);
-  io.schedNum = a->sched_num_events;
-  io.schedTimes = narrow(a->sched_event_times, p->evT, B * QMGPU_MAX_EVENTS);   // the 1e300 padding becomes +inf: still "never"
-  io.schedModes = a->sched_modes;
-  io.warmX = narrow(a->warm_x, p->warmX, B * N1 * 30);
-  io.warmU = narrow(a->warm_u, p->warmU, B * N * 30);
-  io.eeContact = narrow(a->ee_contact_ref, p->contact, B * K * 6);
-  io.outT = p->outT; io.outX = p->outX; io.outU = p->outU; io.outMode = a->out_mode; io.outStats = a->out_stats ? p->outStats : nullptr;
-  io.algorithm = a->algorithm;
-  if (a->algorithm == QMGPU_ALG_DDP) {
-    ensureDdpBuffers(p->m, size_t(p->maxBatch), size_t(p->maxNodes), p->alloc);
-    enqueueDdpKernels(s, p->m, io, ddpTrials, ev);
-  } else {
-    enqueueMpcKernels(s, p->m, io, iterations, false, ev);
-  }
+  const MpcIo io = makeMpcIo(*a, settings.dt, p->in, narrow, p->outT, p->outX, p->outU, a->out_stats ? p->outStats : nullptr);
+  enqueueMpcSolve(s, p->m, io, settings, false, ev, alloc);
   auto widen = [&](const float* src, double* dst, size_t n) { QM_LAUNCH(widen_kernel, unsigned((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024), 256, s, src, dst, n); };
   widen(p->outT, a->out_t, B * N1);
   widen(p->outX, a->out_x, B * N1 * 30);
   widen(p->outU, a->out_u, B * N * 30);
   if (a->out_stats) widen(p->outStats, a->out_stats, B * QMGPU_NSTATS);
-  return hipGetLastError() == hipSuccess;
+  HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace qmk

@@ -19,6 +19,11 @@ def test_header_symbols_exported(hip_lib):
     for name in declared:
         assert hasattr(hip_lib, name), f"{name} declared in qmgpu.h but not exported"
     assert sorted(abi.SYMBOLS) == declared
+    # every function that takes arguments has its argtypes declared, as many as the header's declaration has parameters (nothing goes through ctypes' default conversions)
+    for name, params in re.findall(r"\b(qmgpu_[a-z_0-9]+)\s*\(([^)]*)\)", re.sub(r"/\*.*?\*/", "", header, flags=re.S)):
+        count = 0 if params.strip() == "void" else params.count(",") + 1
+        argtypes = getattr(hip_lib, name).argtypes
+        assert len(argtypes or ()) == count, f"{name}: {count} parameters in qmgpu.h, argtypes {argtypes}"
 
 
 def test_struct_layout_matches_c():

@@ -15,6 +15,7 @@
 // row c of L); lane q < r owns task row q of AZ (residual).
 #pragma once
 #include "gpu_rt.h"
+#include "wbc_lds.h"
 
 namespace qmk {
 
@@ -26,8 +27,6 @@ constexpr double QP_REG = 1e-12;             // HoQp's regulariser (HoQp.cpp:66)
 constexpr double QP_LAM_TOL = 8.0;           // = kAsLamTol of the CPU restatement
 constexpr int QP_MAX_CHANGES = 100;          // nWSR of HoQp.cpp:141
 constexpr int QP_HELD_CAP = 4;               // the held-variable form of the first level is given up beyond this many iterations (status 6; = kHeldFormMaxIterations of the CPU restatement): the interior point takes over
-constexpr int QP_KMAX = 28;                  // pinned rows the small system holds (S: QP_KMAX x (QP_KMAX + 1) doubles of LDS)
-constexpr int QP_SLD = QP_KMAX + 1;
 constexpr double QP_STAGNATION_MU = 1e-10;
 
 struct QpIo {
@@ -39,9 +38,9 @@ struct QpIo {
   double* Kt;           // [36][ldk] scratch: K tiles, then the rows of L, then the rows of T of the pinned set
   double* wtL;          // [64] scratch: row weights
   double* zs;           // [36] out: solution (lanes >= n write 0)
-  double* red;          // [512] exchange lines of qpSolve: broadcasts, the small system's right-hand side, column-sum partials, task residual
-  double* fork;         // [1] command word of the fork-join with the three helper wavefronts (wbc_kernel): 0 = leave, NP = K tiles of that size
-  double* S;            // [QP_KMAX][QP_SLD] scratch: the small system of the pinned rows
+  double* red;          // the exchange block (wbc_lds.h: WX_*): broadcasts, the small system's right-hand side, column-sum partials, task residual
+  double* fork;         // [1] command word of the fork-join with the three helper wavefronts (wbc_kernel): CTL_FORK of wbc_lds.h, or null where the wavefront solves alone
+  double* S;            // [QP_KMAX][QP_SLD] scratch: the small system of the pinned rows (WO_S)
   double* Tp;           // [QP_KMAX][ldk] scratch: T_P = L^-1 DZ_P', one row per pinned row (slot order)
 };
 
@@ -85,30 +84,31 @@ template <int NP, int LDZ_, int LDK_> __device__ __forceinline__ void ipmKTiles(
     }
 }
 
-// sum over 14 of the 56 rows of DZ[i][column of this lane] * bc[i] (bc: io.red[0..63], published by the solving wavefront): the share
-// of wavefront `wave` of a 56-row column sum; the partial sums meet in io.red[128 + 64 wave + lane]
+// sum over 14 of the 56 rows of DZ[i][column of this lane] * bc[i] (bc: the broadcast line WX_BC, published by the solving wavefront): the share
+// of wavefront `wave` of a 56-row column sum; the partial sums meet in line `wave` of WX_COLSUM
 template <int LDZ_> __device__ __forceinline__ void ipmColSumShare(const QpIo& io, int wave, int lane) {
   const int colL = lane < 36 ? lane : 0, i0 = 14 * wave;
-  const double* bc = io.red;
+  const double* bc = io.red + WX_BC.off;
   double t[14], g[14];
 #pragma unroll
   for (int q = 0; q < 14; ++q) { t[q] = io.DZ[(i0 + q) * LDZ_ + colL]; g[q] = bc[i0 + q]; }
   double a0 = 0.0, a1 = 0.0;
 #pragma unroll
   for (int q = 0; q < 14; q += 2) { a0 += t[q] * g[q]; a1 += t[q + 1] * g[q + 1]; }
-  io.red[128 + 64 * wave + lane] = a0 + a1;
+  io.red[WX_COLSUM.off + 64 * wave + lane] = a0 + a1;
 }
 // the whole sum on four wavefronts (fork-join as for the K tiles), or on this one
 template <int LDZ_> __device__ __forceinline__ double ipmColSum(const QpIo& io, int lane) {
   if (io.fork) {
-    io.fork[0] = 200.0;
+    io.fork[0] = double(FORK_COLSUM);
     QM_LDS_BARRIER();
     ipmColSumShare<LDZ_>(io, 0, lane);
     QM_LDS_BARRIER();
-    return (io.red[128 + lane] + io.red[192 + lane]) + (io.red[256 + lane] + io.red[320 + lane]);
+    const double* part = io.red + WX_COLSUM.off;
+    return (part[lane] + part[64 + lane]) + (part[128 + lane] + part[192 + lane]);
   }
   double s = 0.0;
-  for (int w = 0; w < 4; ++w) { ipmColSumShare<LDZ_>(io, w, lane); QM_WAVE_SYNC(); s += io.red[128 + 64 * w + lane]; }
+  for (int w = 0; w < 4; ++w) { ipmColSumShare<LDZ_>(io, w, lane); QM_WAVE_SYNC(); s += io.red[WX_COLSUM.off + 64 * w + lane]; }
   return s;
 }
 
@@ -152,6 +152,26 @@ template <int NP, int J> struct IpmFactorStep {
 };
 
 struct QpOff { int G, AZ, rhat, DZ, fhat, Kt, wtL, zs, red, fork, S, Tp; };
+// The arrays of one level solve as offsets into the carve (wbc_lds.h): only the task rows and their residual differ from solve to solve.
+__device__ __forceinline__ QpOff qpOffOf(int azOff, int rhatOff) {
+  QpOff o;
+  o.G = WL_G.off; o.AZ = azOff; o.rhat = rhatOff; o.DZ = WL_DZ.off; o.fhat = WL_FHAT.off; o.Kt = WL_K.off; o.wtL = WL_WT.off; o.zs = WL_ZS.off;
+  o.red = WL_RED.off; o.fork = WL_CTL.off + CTL_FORK; o.S = WO_S.off; o.Tp = WL_TP.off;
+  return o;
+}
+// ... and re-based on an LDS base pointer
+__device__ __forceinline__ QpIo qpIoAt(double* base, const QpOff& o) {
+  QpIo io;
+  io.G = base + o.G; io.AZ = base + o.AZ; io.rhat = base + o.rhat; io.DZ = base + o.DZ; io.fhat = base + o.fhat; io.Kt = base + o.Kt; io.wtL = base + o.wtL; io.zs = base + o.zs;
+  io.red = base + o.red; io.fork = base + o.fork; io.S = base + o.S; io.Tp = base + o.Tp;
+  return io;
+}
+// ... for the helper wavefronts: their shares read G, DZ, the weights, K and the exchange block only; what they have no business with stays null, so that a mistaken read faults
+__device__ __forceinline__ QpIo qpIoHelpers(double* base) {
+  QpIo io = qpIoAt(base, qpOffOf(0, 0));
+  io.AZ = nullptr; io.rhat = nullptr; io.S = nullptr; io.Tp = nullptr;
+  return io;
+}
 struct QpResult { int status; int ipmIterations, iterations; bool strong; unsigned long long pinMask; bool warmRefuted; bool heldTried; };   // pinMask: the rows pinned at the solution (status 0); status: 0 ok | 1 working-set changes exhausted | 2 numerical failure | 3 final check failed | 4 more pinned rows than the small system holds | 5 the cost wants held variables moved | 6 held-variable form given up (QP_HELD_CAP); heldTried: variables were held
 
 // A called function, not inlined: the kernel around it sits at 512 VGPRs with scratch, and three inlined instantiations of this body add
@@ -173,12 +193,12 @@ struct QpResult { int status; int ipmIterations, iterations; bool strong; unsign
 template <int NP, int LDZ_, int LDK_>
 __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, int m0, bool own, bool rowOnIn, double sigma0, bool tryHeld, unsigned long long warm, const double* warmZ, bool lit, int lane) {
   QM_DYNAMIC_LDS(ldsBase);
-  const QpIo io{ldsBase + off.G, ldsBase + off.AZ, ldsBase + off.rhat, ldsBase + off.DZ, ldsBase + off.fhat, ldsBase + off.Kt, ldsBase + off.wtL, ldsBase + off.zs, ldsBase + off.red, ldsBase + off.fork, ldsBase + off.S, ldsBase + off.Tp};
+  const QpIo io = qpIoAt(ldsBase, off);
   enum { ST_I = 0, ST_P = 1, ST_V = 2 };
   const double* G = io.G; const double* DZ = io.DZ; const double* AZ = io.AZ;
-  double* bc = io.red;              // [0..63] broadcast line (z, multipliers, u, v ...)
-  double* ms = io.red + 64;         // [64..127] the small system's right-hand side / solution, by slot
-  double* resL = io.red + 384;      // [384..447] task residual, by task row; [448..511] |.| version for the rounding bound
+  double* bc = io.red + WX_BC.off;       // broadcast line (z, multipliers, u, v ...)
+  double* ms = io.red + WX_MS.off;       // the small system's right-hand side / solution, by slot
+  double* resL = io.red + WX_RES.off;    // task residual, by task row
   auto allSum = [&](double v) { return qmAllSum(v); };
   auto allMax = [&](double v) { return qmAllMax(v); };
   auto allMin = [&](double v) { return qmAllMin(v); };
@@ -264,7 +284,7 @@ __device__ __attribute__((noinline)) QpResult qpSolve(QpOff off, int n, int r, i
     if (lane < 56) io.wtL[lane] = wt;
     QM_WAVE_SYNC();
     if (NP > 16 && io.fork) {   // several tiles: the helper wavefronts take theirs between two workgroup barriers
-      io.fork[0] = double(NP);
+      io.fork[0] = double(forkKTiles(NP));
       QM_LDS_BARRIER();
       ipmKTiles<NP, LDZ_, LDK_>(io, 0, lane);
       QM_LDS_BARRIER();

@@ -20,6 +20,7 @@
 #include "gpu_rt.h"
 #include "linesearch_kernel.h"  // DblIn
 #include "sweep_dev.h"
+#include "wbc_lds.h"
 #include "qp_dev.h"
 #include "wave_gemm.h"
 
@@ -34,36 +35,7 @@ struct WbcArgs {
   unsigned long long* workingSet;   // [batch][QMGPU_WBC_STATE_WORDS] in / out or null: the working sets of the previous tick (qmgpu_wbc_args::working_set)
 };
 
-constexpr int ND = 36, NVV = 24, MAXR = 22, MAXM = 56;
-constexpr int LDZ = 37, LDK = 37;
-// ---- LDS carve (doubles)
-constexpr int W_IN = 0;                          // rbd[55] xDes[30] uDes[30] inputLast[30] -> 160
-constexpr int W_Q = W_IN + 160;                  // qM vM qD vD [4][24]
-constexpr int W_BODY = W_Q + 96;                 // per body: R9 p3 c3 I6 w3 al3 vo3 ao3 = 33  -> 19*33 = 627 (+pad)
-constexpr int W_DOF = W_BODY + 640;              // dof axis[24][3], origin[24][3]
-constexpr int W_WR = W_DOF + 144;                // body wrench force[19][3] torque[19][3]
-constexpr int W_M = W_WR + 120;                  // M [24][24]
-constexpr int W_NLE = W_M + 576;                 // nle[24]
-constexpr int W_JF = W_NLE + 24;                 // feet J [12][24]
-constexpr int W_JA = W_JF + 288;                 // arm J [6][24]
-constexpr int W_MISC = W_JA + 144;               // see offsets below (144)
-constexpr int W_A = W_MISC + 144;                // task A [MAXR][36], b[MAXR]
-constexpr int W_B = W_A + MAXR * ND;
-constexpr int W_D0 = W_B + 24;                   // D0 [MAXM][36]
-constexpr int W_F0 = W_D0 + MAXM * ND;           // f0[56], slack solution v0[56]
-constexpr int W_Z = W_F0 + 2 * MAXM;             // Z [36][LDZ]
-constexpr int W_ZN = W_Z + ND * LDZ;             // Znew
-constexpr int W_AZ = W_ZN + ND * LDZ;            // A Z [MAXR][LDZ]
-constexpr int W_DZ = W_AZ + MAXR * LDZ;          // D0 Z [MAXM][LDZ]
-constexpr int W_K = W_DZ + MAXM * LDZ;           // K / Cholesky [36][LDK]
-constexpr int W_G = W_K + ND * LDK;              // G = AZ^T AZ + eps [36][LDK]
-constexpr int W_VH = W_G + ND * LDK;             // Householder vectors [MAXR][40]
-constexpr int W_VEC = W_VH + MAXR * 40;          // vectors: x[36] z[36] g[36] rd[36] rhs[36] dz[36] fhat[56] lam[56] wt[56] tz[56] red[1024]
-constexpr int W_BODY2 = W_VEC + 6 * 36 + 4 * 56 + 1024 + 8;   // (red[1024]: the level solver's exchange lines red[0..511] (qp_dev.h: qpSolve), the fork-join's job red[512..521]) body / dof tables of the desired pass (wavefront 1)
-constexpr int W_DOF2 = W_BODY2 + 640;
-constexpr int W_TP = W_DOF2 + 144;               // T_P = L^-1 DZ_P' of the level solver's pinned rows [QP_KMAX][LDK] (round 6; until then over the K square, one row at a time)
-constexpr int WBC_LDS_DOUBLES = W_TP + QP_KMAX * LDK;
-constexpr int WBC_LDS_BYTES = WBC_LDS_DOUBLES * 8;
+// (the LDS carve, its sub-regions and overlays: wbc_lds.h)
 constexpr int WBC_THREADS = 256;   // the solving wavefront + three helpers (one per SIMD of the CU)
 // misc block
 constexpr int MI_FOOTPM = 0, MI_FOOTVM = 12, MI_FOOTDJV = 24, MI_FOOTPD = 36, MI_FOOTVD = 48, MI_EEPM = 60, MI_EEVM = 63, MI_EEWM = 66, MI_EEDJL = 69, MI_EEDJA = 72,
@@ -204,15 +176,13 @@ __device__ inline void ldsCholSolve(const double* L, int n, double* y, int lane)
 // unit rows: exact ties are the rule, and the basis -- the coordinates the minimum-norm representative of a level is taken in -- depends on the order.  The kernels and the
 // CPU restatement of the tests take the same decisions with the same roundings.  Result: N (n x nNew, row stride LDK) in K; returns nNew.
 // Also used for the implied equalities of a level (rows = the strongly active inequality rows, wbc_kernel).  A called function: three call sites, one copy; the arrays
-// arrive as offsets into the dynamic LDS (qp_dev.h: qpSolve).  redOff is not read: it stays in the signature because dropping it changes how wbc_kernel is compiled.
-__device__ __attribute__((noinline)) int wbcNullSpace(int rowsOff, int r, int n, int kOff, int vhOff, int redOff, int lane) {
+// arrive as offsets into the dynamic LDS, as for qpSolve; redOff: the exchange block, whose int regions hold the index tables (the chunks' candidate magnitudes: WO_XCHGV of the carve).
+__device__ __attribute__((noinline)) int wbcNullSpace(int rowsOff, int r, int n, int kOff, int redOff, int lane) {
   QM_DYNAMIC_LDS(ldsBase);
-  double* rows = ldsBase + rowsOff; double* K = ldsBase + kOff; double* Vh = ldsBase + vhOff;
+  double* rows = ldsBase + rowsOff; double* K = ldsBase + kOff; double* red = ldsBase + redOff;
   QM_TICK_DECL;
-  static_assert(MAXR <= 24 && ND <= 36 && 128 + 64 + 32 <= MAXR * 40, "index tables of the null-space step fit the region they are carved from");
   {
-      int* ip = reinterpret_cast<int*>(Vh);        // colPerm[36] | rowOf[MAXR] | pivOk[MAXR] | freePos[36]  (the reflector table of round 3: free here)
-      int* colPerm = ip; int* rowOf = ip + 40; int* pivOk = ip + 64; int* freePos = ip + 96;
+      int* colPerm = ldsInts(red, WX_COLPERM); int* rowOf = ldsInts(red, WX_ROWOF); int* pivOk = ldsInts(red, WX_PIVOK); int* freePos = ldsInts(red, WX_FREEPOS);
       const int size = r < n ? r : n;
       // Lanes: row i of A Z is worked on by up to three lanes, i, r + i and 2 r + i ("chunks"), each eliminating a contiguous third of the column positions behind the pivot
       // (r <= 21: three chunks, 22: two) -- with one lane per row only r of the 64 lanes worked and a step was 35 dependent LDS round trips long.  Same arithmetic per
@@ -222,7 +192,7 @@ __device__ __attribute__((noinline)) int wbcNullSpace(int rowsOff, int r, int n,
       const int chunk = (lane >= r ? 1 : 0) + (lane >= 2 * r ? 1 : 0);
       const bool active = lane < nChunk * r;
       const int rowIdx = active ? lane - chunk * r : 0;
-      double* xchgV = Vh + 128; int* xchgJ = reinterpret_cast<int*>(Vh + 192);   // exchange of the chunks' candidates (64 doubles, 64 ints; beyond the index tables)
+      double* xchgV = ldsBase + WO_XCHGV.off; int* xchgJ = ldsInts(red, WX_XCHGJ);   // exchange of the chunks' candidates
       int rowPos = rowIdx;
       int colPermReg = lane;     // lane j: the original column at position j (swapped between lanes with v_readlane; LDS copy after the loop)
       int rowOfReg = 0;          // lane k: the row that gave pivot k
@@ -360,154 +330,106 @@ __device__ __attribute__((noinline)) int wbcNullSpace(int rowsOff, int r, int n,
   }
 }
 
-__global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(WbcArgs a) {
-  QM_DYNAMIC_LDS(lds);
-#if defined(QM_WBC_OPAQUE_LDS) && !defined(QMGPU_HOST_EMULATION)
-  // Build variant (tools/wbc_variants.py, DESIGN.md section 4.7): the arrays of the carve are addressed through one opaque address-space-3 base
-  // register (round 2: wrong torques with IPRA on, correct with it off).
-  QM_OPAQUE_LDS(double, ldsO, lds);
-  double* carve = (double*)ldsO;
-#else
-  double* carve = lds;
-#endif
-  QM_POISON_LDS(lds, WBC_LDS_DOUBLES);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, inst = blockIdx.x;
-  // (the model constants reach this kernel through ~800 vector loads per instance -- after its first global store a kernel cannot use scalar loads for them,
-  //  gpu_rt.h: QM_CONSTANT_REF; a copy of the struct in LDS was measured in round 3 and not kept: 0.4405 -> 0.4445 ms, the loads are batched well enough)
-  const qmgpu_model& md = a.P->model;
-  const qmgpu_settings& st = a.P->settings;
-  double fe[3] = {0.0, 0.0, 0.0};   // external force on the arm end-effector (force tracking; zero otherwise)
-  if (a.eeForce) for (int i = 0; i < 3; ++i) fe[i] = a.eeForce[size_t(inst) * 3 + i];
-  double* in = carve + W_IN; double* rbd = in; double* xDes = in + 55; double* uDes = in + 85; double* il = in + 115;
-  double* qM = carve + W_Q; double* vM = qM + 24; double* qD = qM + 48; double* vD = qM + 72;
-  double* body = carve + W_BODY; double* dof = carve + W_DOF; double* wr = carve + W_WR; double* M = carve + W_M; double* nle = carve + W_NLE;
-  double* Jf = carve + W_JF; double* Ja = carve + W_JA; double* mi = carve + W_MISC;
-  double* A = carve + W_A; double* bvec = carve + W_B; double* D0 = carve + W_D0; double* f0 = carve + W_F0; double* v0 = f0 + MAXM;
-  double* Z = carve + W_Z; double* Zn = carve + W_ZN; double* AZ = carve + W_AZ; double* DZ = carve + W_DZ; double* K = carve + W_K; double* G = carve + W_G; double* Vh = carve + W_VH;
-  double* xs = carve + W_VEC; double* zs = xs + 36; double* gs = zs + 36; double* rds = gs + 36; double* rhs = rds + 36; double* dzs = rhs + 36;
-  double* fhat = carve + (W_VEC + 6 * 36); double* lam = fhat + 56; double* wt = lam + 56; double* tzv = wt + 56; double* red = carve + (W_VEC + 6 * 36 + 4 * 56); double* ctl = red + 1024;
-
-  // Wavefront 0 solves the instance; the other three sit on the CU's idle SIMDs and take their share of the matrix-core tiles of the
-  // interior point between two workgroup barriers (qp_dev.h: ipmKTiles).  Command word: ctl[4] (0 = leave).
-  double* forkCmd = ctl + 4; double* forkJob = red + 512;   // (behind the level solver's red[0..511]: qp_dev.h, qpSolve)
-  // ---- S5: desired pass (WbcBase.cpp:205-237), on wavefront 1 while wavefront 0 runs the measured pass, M, nle and the Jacobians: it has its own
-  //      body / dof tables and writes only v_des of the base and the desired entries of mi, none of which is read before the join after S4.
-  //      v_des base from the centroidal map (WbcBase.cpp:217-219) with the MPC's own sweep.
-  auto desiredPass = [&](double* body, double* dof) {
-    {
-      double k1z[12];
-  #pragma unroll
-      for (int i = 0; i < 12; ++i) k1z[i] = 0.0;
-      const DblIn din{xDes, uDes, 0.0, k1z};
-      double f[12];
-      BaseMotion<double> bm;
-      centroidalSweep<double>(md, st.gravity, din, [&](int, Vec3<double>, Vec3<double>) {}, [&](Vec3<double>, const Mat3<double>&) { return Vec3<double>(); }, f, bm);
-      if (lane == 0) for (int i = 0; i < 6; ++i) vD[i] = f[6 + i];
-    }
-    QM_WAVE_SYNC();
-    bodyPass(md, qD, vD, mi + MI_JACC, body, dof, lane);
-    QM_WAVE_SYNC();
-    if (lane == 0) {
-      // momentum rate produced by (v_des, joint accelerations, zero base acceleration): Adot v + Aj qdd_j (WbcBase.cpp:231-234)
-      double ct[3] = {0, 0, 0};
-      for (int b = 0; b < QMGPU_NB; ++b) for (int i = 0; i < 3; ++i) ct[i] += md.mass[b] * body[b * 33 + 12 + i];
-      for (int i = 0; i < 3; ++i) ct[i] /= md.total_mass;
-      double hl[3] = {0, 0, 0}, ha[3] = {0, 0, 0}, Ic[6] = {0, 0, 0, 0, 0, 0};
-      for (int b = 0; b < QMGPU_NB; ++b) {
-        const double* o = body + b * 33;
-        double pos[3], vel[3], acc[3], Iw_w[3], Iw_al[3], t[3], r[3], t2[3];
-        pointKin(md, body, b, md.com[b], pos, vel, acc);
-        symMul(o + 15, o + 21, Iw_w); symMul(o + 15, o + 24, Iw_al); cross3(o + 21, Iw_w, t);
-        for (int i = 0; i < 3; ++i) r[i] = pos[i] - ct[i];
-        double ma[3] = {md.mass[b] * acc[0], md.mass[b] * acc[1], md.mass[b] * acc[2]};
-        cross3(r, ma, t2);
-        const double rr = dot3(r, r), m = md.mass[b];
-        for (int i = 0; i < 3; ++i) { hl[i] += ma[i]; ha[i] += Iw_al[i] + t[i] + t2[i]; }
-        Ic[0] += o[15] + m * (rr - r[0] * r[0]); Ic[1] += o[16] - m * r[0] * r[1]; Ic[2] += o[17] - m * r[0] * r[2];
-        Ic[3] += o[18] + m * (rr - r[1] * r[1]); Ic[4] += o[19] - m * r[1] * r[2]; Ic[5] += o[20] + m * (rr - r[2] * r[2]);
-      }
-      double rl[3] = {-hl[0], -hl[1], -md.total_mass * st.gravity - hl[2]}, ra[3] = {-ha[0], -ha[1], -ha[2]};
-      for (int c = 0; c < 4; ++c) {
-        double pos[3], vel[3], acc[3], t[3], r[3];
-        pointKin(md, body, md.foot_body[c], md.foot_offset[c], pos, vel, acc);
-        for (int i = 0; i < 3; ++i) { mi[MI_FOOTPD + 3 * c + i] = pos[i]; mi[MI_FOOTVD + 3 * c + i] = vel[i]; r[i] = pos[i] - ct[i]; rl[i] += uDes[3 * c + i]; }
-        cross3(r, uDes + 3 * c, t);
-        for (int i = 0; i < 3; ++i) ra[i] += t[i];
-      }
-      {  // external end-effector force in the desired momentum rate (zero without force tracking)
-        double pos[3], vel[3], acc[3], t[3], r[3];
-        pointKin(md, body, md.ee_body, md.ee_offset, pos, vel, acc);
-        for (int i = 0; i < 3; ++i) { r[i] = pos[i] - ct[i]; rl[i] += fe[i]; }
-        cross3(r, fe, t);
-        for (int i = 0; i < 3; ++i) ra[i] += t[i];
-      }
-      // wdot = Ic^-1 ra ; euler acceleration = T^-1 wdot ; linear = rl/m - wdot x (c - p0)
-      Sym3<double> S; S.xx = Ic[0]; S.xy = Ic[1]; S.xz = Ic[2]; S.yy = Ic[3]; S.yz = Ic[4]; S.zz = Ic[5];
-      const Vec3<double> wd = solveSym3(S, Vec3<double>(ra[0], ra[1], ra[2]));
-      const double wdv[3] = {wd.x, wd.y, wd.z}, rc[3] = {ct[0] - qD[0], ct[1] - qD[1], ct[2] - qD[2]};
-      double t[3];
-      cross3(wdv, rc, t);
-      double sz, cz, sy, cy;
-      sincos(qD[3], &sz, &cz); sincos(qD[4], &sy, &cy);
-      const double tmp = (cz * wd.x + sz * wd.y) / cy;
-      for (int i = 0; i < 3; ++i) mi[MI_BACC + i] = rl[i] / md.total_mass - t[i];
-      mi[MI_BACC + 3] = sy * tmp + wd.z; mi[MI_BACC + 4] = cz * wd.y - sz * wd.x; mi[MI_BACC + 5] = tmp;
-      double pos[3], vel[3], acc[3];
-      pointKin(md, body, md.ee_body, md.ee_offset, pos, vel, acc);
-      for (int i = 0; i < 3; ++i) { mi[MI_EEPD + i] = pos[i]; mi[MI_EEVD + i] = vel[i]; }
-      for (int i = 0; i < 9; ++i) mi[MI_EERD + i] = body[md.ee_body * 33 + i];
-    }
-    QM_WAVE_SYNC();
-  };
-  if (wave != 0) {
-    QM_LDS_BARRIER();                                     // inputs and coordinates (S1, S2) are in LDS
-    if (wave == 1) desiredPass(lds + W_BODY2, lds + W_DOF2);
-    const QpIo hio{G, nullptr, nullptr, DZ, fhat, K, wt, zs, red, forkCmd, nullptr, nullptr};
-    for (;;) {
-      QM_LDS_BARRIER();
-      const int op = int(forkCmd[0]);
-      if (op == 0) break;
-      if (op == 36) ipmKTiles<36, LDZ, LDK>(hio, wave, lane);
-      else if (op == 20) ipmKTiles<20, LDZ, LDK>(hio, wave, lane);
-      else if (op == 200) ipmColSumShare<LDZ>(hio, wave, lane);
-      else if (op == 300) {}                                // join of the desired pass
-      else {   // 100 / 101: C = A B / A^T B, described in forkJob (pointers as offsets from the LDS base)
-        const double* jA = lds + int(forkJob[0]); const double* jB = lds + int(forkJob[2]); double* jD = lds + int(forkJob[7]);
-        const int lda = int(forkJob[1]), ldb = int(forkJob[3]), jM = int(forkJob[4]), jN = int(forkJob[5]), jK = int(forkJob[6]), ldd = int(forkJob[8]);
-        if (op == 101) waveGemmTiles<true>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, forkJob[9], wave, lane);
-        else waveGemmTiles<false>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, forkJob[9], wave, lane);
-      }
-      QM_LDS_BARRIER();
-    }
-    return;
+// ---- S5: desired pass (WbcBase.cpp:205-237), on wavefront 1 while wavefront 0 runs the measured pass, M, nle and the Jacobians: it has its own
+//      body / dof tables and writes only v_des of the base and the desired entries of mi, none of which is read before the join after S4.
+//      v_des base from the centroidal map (WbcBase.cpp:217-219) with the MPC's own sweep.  fe: the external force on the arm end-effector.
+__device__ __forceinline__ void wbcDesiredPass(const qmgpu_model& md, const qmgpu_settings& st, const double* xDes, const double* uDes, const double* fe, const double* qD, double* vD, double* mi,
+                                               double* body, double* dof, int lane) {
+  {
+    double k1z[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) k1z[i] = 0.0;
+    const DblIn din{xDes, uDes, 0.0, k1z};
+    double f[12];
+    BaseMotion<double> bm;
+    centroidalSweep<double>(md, st.gravity, din, [&](int, Vec3<double>, Vec3<double>) {}, [&](Vec3<double>, const Mat3<double>&) { return Vec3<double>(); }, f, bm);
+    if (lane == 0) for (int i = 0; i < 6; ++i) vD[i] = f[6 + i];
   }
-  // C (M x N, LDS) = op(A) B with the four wavefronts sharing the tiles
-  auto forkGemm = [&](bool ta, const double* jA, int lda, const double* jB, int ldb, int jM, int jN, int jK, double* jD, int ldd, double diagAdd) {
-    if (lane == 0) {
-      forkJob[0] = double(jA - lds); forkJob[1] = lda; forkJob[2] = double(jB - lds); forkJob[3] = ldb; forkJob[4] = jM; forkJob[5] = jN; forkJob[6] = jK;
-      forkJob[7] = double(jD - lds); forkJob[8] = ldd; forkJob[9] = diagAdd; forkCmd[0] = ta ? 101.0 : 100.0;
+  QM_WAVE_SYNC();
+  bodyPass(md, qD, vD, mi + MI_JACC, body, dof, lane);
+  QM_WAVE_SYNC();
+  if (lane == 0) {
+    // momentum rate produced by (v_des, joint accelerations, zero base acceleration): Adot v + Aj qdd_j (WbcBase.cpp:231-234)
+    double ct[3] = {0, 0, 0};
+    for (int b = 0; b < QMGPU_NB; ++b) for (int i = 0; i < 3; ++i) ct[i] += md.mass[b] * body[b * 33 + 12 + i];
+    for (int i = 0; i < 3; ++i) ct[i] /= md.total_mass;
+    double hl[3] = {0, 0, 0}, ha[3] = {0, 0, 0}, Ic[6] = {0, 0, 0, 0, 0, 0};
+    for (int b = 0; b < QMGPU_NB; ++b) {
+      const double* o = body + b * 33;
+      double pos[3], vel[3], acc[3], Iw_w[3], Iw_al[3], t[3], r[3], t2[3];
+      pointKin(md, body, b, md.com[b], pos, vel, acc);
+      symMul(o + 15, o + 21, Iw_w); symMul(o + 15, o + 24, Iw_al); cross3(o + 21, Iw_w, t);
+      for (int i = 0; i < 3; ++i) r[i] = pos[i] - ct[i];
+      double ma[3] = {md.mass[b] * acc[0], md.mass[b] * acc[1], md.mass[b] * acc[2]};
+      cross3(r, ma, t2);
+      const double rr = dot3(r, r), m = md.mass[b];
+      for (int i = 0; i < 3; ++i) { hl[i] += ma[i]; ha[i] += Iw_al[i] + t[i] + t2[i]; }
+      Ic[0] += o[15] + m * (rr - r[0] * r[0]); Ic[1] += o[16] - m * r[0] * r[1]; Ic[2] += o[17] - m * r[0] * r[2];
+      Ic[3] += o[18] + m * (rr - r[1] * r[1]); Ic[4] += o[19] - m * r[1] * r[2]; Ic[5] += o[20] + m * (rr - r[2] * r[2]);
+    }
+    double rl[3] = {-hl[0], -hl[1], -md.total_mass * st.gravity - hl[2]}, ra[3] = {-ha[0], -ha[1], -ha[2]};
+    for (int c = 0; c < 4; ++c) {
+      double pos[3], vel[3], acc[3], t[3], r[3];
+      pointKin(md, body, md.foot_body[c], md.foot_offset[c], pos, vel, acc);
+      for (int i = 0; i < 3; ++i) { mi[MI_FOOTPD + 3 * c + i] = pos[i]; mi[MI_FOOTVD + 3 * c + i] = vel[i]; r[i] = pos[i] - ct[i]; rl[i] += uDes[3 * c + i]; }
+      cross3(r, uDes + 3 * c, t);
+      for (int i = 0; i < 3; ++i) ra[i] += t[i];
+    }
+    {  // external end-effector force in the desired momentum rate (zero without force tracking)
+      double pos[3], vel[3], acc[3], t[3], r[3];
+      pointKin(md, body, md.ee_body, md.ee_offset, pos, vel, acc);
+      for (int i = 0; i < 3; ++i) { r[i] = pos[i] - ct[i]; rl[i] += fe[i]; }
+      cross3(r, fe, t);
+      for (int i = 0; i < 3; ++i) ra[i] += t[i];
+    }
+    // wdot = Ic^-1 ra ; euler acceleration = T^-1 wdot ; linear = rl/m - wdot x (c - p0)
+    Sym3<double> S; S.xx = Ic[0]; S.xy = Ic[1]; S.xz = Ic[2]; S.yy = Ic[3]; S.yz = Ic[4]; S.zz = Ic[5];
+    const Vec3<double> wd = solveSym3(S, Vec3<double>(ra[0], ra[1], ra[2]));
+    const double wdv[3] = {wd.x, wd.y, wd.z}, rc[3] = {ct[0] - qD[0], ct[1] - qD[1], ct[2] - qD[2]};
+    double t[3];
+    cross3(wdv, rc, t);
+    double sz, cz, sy, cy;
+    sincos(qD[3], &sz, &cz); sincos(qD[4], &sy, &cy);
+    const double tmp = (cz * wd.x + sz * wd.y) / cy;
+    for (int i = 0; i < 3; ++i) mi[MI_BACC + i] = rl[i] / md.total_mass - t[i];
+    mi[MI_BACC + 3] = sy * tmp + wd.z; mi[MI_BACC + 4] = cz * wd.y - sz * wd.x; mi[MI_BACC + 5] = tmp;
+    double pos[3], vel[3], acc[3];
+    pointKin(md, body, md.ee_body, md.ee_offset, pos, vel, acc);
+    for (int i = 0; i < 3; ++i) { mi[MI_EEPD + i] = pos[i]; mi[MI_EEVD + i] = vel[i]; }
+    for (int i = 0; i < 9; ++i) mi[MI_EERD + i] = body[md.ee_body * 33 + i];
+  }
+  QM_WAVE_SYNC();
+}
+
+// The helper wavefronts' command loop: between two workgroup barriers they take their share of what the solving wavefront announces in forkCmd[0]
+// (the K tiles and column sums of the interior point, a product described in forkJob), until FORK_LEAVE.
+__device__ __forceinline__ void wbcHelperLoop(double* lds, double* carve, const double* forkCmd, const double* forkJob, int wave, int lane) {
+  const QpIo hio = qpIoHelpers(carve);
+  for (;;) {
+    QM_LDS_BARRIER();
+    const int op = int(forkCmd[0]);
+    if (op == FORK_LEAVE) break;
+    if (op == forkKTiles(36)) ipmKTiles<36, LDZ, LDK>(hio, wave, lane);
+    else if (op == forkKTiles(20)) ipmKTiles<20, LDZ, LDK>(hio, wave, lane);
+    else if (op == FORK_COLSUM) ipmColSumShare<LDZ>(hio, wave, lane);
+    else if (op == FORK_JOIN) {}                          // join of the desired pass
+    else {   // FORK_GEMM / FORK_GEMM_T: C = A B / A^T B, described in forkJob (pointers as offsets from the LDS base)
+      const double* jA = lds + int(forkJob[FJ_A]); const double* jB = lds + int(forkJob[FJ_B]); double* jD = lds + int(forkJob[FJ_D]);
+      const int lda = int(forkJob[FJ_LDA]), ldb = int(forkJob[FJ_LDB]), jM = int(forkJob[FJ_M]), jN = int(forkJob[FJ_N]), jK = int(forkJob[FJ_K]), ldd = int(forkJob[FJ_LDD]);
+      if (op == FORK_GEMM_T) waveGemmTiles<true>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, forkJob[FJ_DIAG], wave, lane);
+      else waveGemmTiles<false>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, forkJob[FJ_DIAG], wave, lane);
     }
     QM_LDS_BARRIER();
-    if (ta) waveGemmTiles<true>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, diagAdd, 0, lane);
-    else waveGemmTiles<false>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, diagAdd, 0, lane);
-    QM_LDS_BARRIER();
-  };
-  const int mode = a.mode[inst];
-  const double period = a.period[inst], time = a.time[inst];
-  bool contact[4]; int nst = 0;
-  for (int c = 0; c < 4; ++c) { contact[c] = contactOf(mode, c); nst += contact[c] ? 1 : 0; }
-  const int nsw = 4 - nst;
+  }
+}
 
-  for (int e = lane; e < MAXM * LDZ; e += 64) DZ[e] = 0.0;  // rows >= m0 are never written: the interior point only needs them finite
-  QM_TICK_DECL;
-#ifdef QM_RICCATI_TIMING
-  const unsigned long long qmStart = clock64();
-#endif
-  // ---- S1: inputs
+// ---- S1: inputs
+__device__ __forceinline__ void wbcLoadInputs(const WbcArgs& a, int inst, double* rbd, double* xDes, double* uDes, double* il, int lane) {
   if (lane < 55) rbd[lane] = a.rbd[size_t(inst) * 55 + lane];
   if (lane < 30) { xDes[lane] = a.xDes[size_t(inst) * 30 + lane]; uDes[lane] = a.uDes[size_t(inst) * 30 + lane]; il[lane] = a.inputLast[size_t(inst) * 30 + lane]; }
-  QM_WAVE_SYNC();
-  // ---- S2: Pinocchio coordinates of the measured state (WbcBase.cpp:150-156)
+}
+// ---- S2: Pinocchio coordinates of the measured state (WbcBase.cpp:150-156), the desired joint coordinates and accelerations
+__device__ __forceinline__ void wbcCoordinates(const double* rbd, const double* xDes, const double* uDes, const double* il, double period, double* qM, double* vM, double* qD, double* vD, double* mi, int lane) {
   if (lane == 0) {
     for (int i = 0; i < 3; ++i) { qM[i] = rbd[3 + i]; qM[3 + i] = rbd[i]; vM[i] = rbd[24 + 3 + i]; }
     for (int j = 0; j < 18; ++j) { qM[6 + j] = rbd[6 + j]; vM[6 + j] = rbd[24 + 6 + j]; }
@@ -519,11 +441,9 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
     for (int j = 0; j < 18; ++j) { qD[6 + j] = xDes[12 + j]; vD[6 + j] = uDes[12 + j]; mi[MI_JACC + j] = (uDes[12 + j] - il[12 + j]) / period; }
     for (int i = 0; i < 6; ++i) qD[i] = xDes[6 + i];
   }
-  if (lane < 30) a.inputLast[size_t(inst) * 30 + lane] = uDes[lane];  // WbcBase.cpp:225
-  QM_LDS_BARRIER();      // wavefront 1 starts the desired pass (S5) from here
-
-  QM_TICK(0);
-  // ---- S3: measured pass (zero generalized acceleration -> bias terms)
+}
+// ---- S3: measured pass (zero generalized acceleration -> bias terms) and the body wrenches
+__device__ __forceinline__ void wbcMeasuredPass(const qmgpu_model& md, const qmgpu_settings& st, const double* qM, const double* vM, double* body, double* dof, double* wr, int lane) {
   bodyPass(md, qM, vM, nullptr, body, dof, lane);
   QM_WAVE_SYNC();
   // body wrenches for the nonlinear effects: f = m (a_c + g), n = I alpha + w x I w
@@ -534,13 +454,12 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
     symMul(o + 15, o + 21, Iw_w); symMul(o + 15, o + 24, Iw_al); cross3(o + 21, Iw_w, t);
     for (int i = 0; i < 3; ++i) { wr[lane * 3 + i] = md.mass[lane] * (acc[i] + (i == 2 ? st.gravity : 0.0)); wr[57 + lane * 3 + i] = Iw_al[i] + t[i]; }
   }
-  QM_WAVE_SYNC();
-  QM_TICK(1);
-  // ---- S4: lane k = generalized velocity k: nle_k, column k of M, Jacobian columns
-  // The Jacobian column of every (body b, velocity i) pair at the body's centre of mass is formed ONCE (by lane i, into the LDS that Z / Z_new / A Z
-  // take over later) instead of by every lane for every pair: M[i][k] = sum_b J_bi^T diag(m_b, I_b) J_bk is then six multiply-adds per term.
-  double* JL = Z;   // [19][24][6] = 2736 doubles over Z, Z_new and the head of A Z (contiguous, all unused before the first level)
-  static_assert(W_ZN == W_Z + ND * LDZ && W_AZ == W_ZN + ND * LDZ && QMGPU_NB * NVV * 6 <= 2 * ND * LDZ + MAXR * LDZ, "Jacobian columns fit the Z / Z_new / A Z regions");
+}
+// ---- S4: lane k = generalized velocity k: nle_k, column k of M, Jacobian columns; the feet's and the end-effector's kinematics into mi
+// The Jacobian column of every (body b, velocity i) pair at the body's centre of mass is formed ONCE (by lane i, into JL) instead of by every lane
+// for every pair: M[i][k] = sum_b J_bi^T diag(m_b, I_b) J_bk is then six multiply-adds per term.
+__device__ __forceinline__ void wbcInertiaAndJacobians(const qmgpu_model& md, const double* fe, const double* body, const double* dof, const double* wr, double* JL, double* M, double* nle, double* Jf, double* Ja,
+                                                       double* mi, int lane) {
   if (lane < NVV) {
 #pragma unroll 1
     for (int b = 0; b < QMGPU_NB; ++b) {
@@ -613,22 +532,9 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
     }
     for (int i = 0; i < 9; ++i) mi[MI_EERM + i] = o[i];
   }
-  QM_WAVE_SYNC();
-
-  QM_TICK(2);
-  // ---- S5 runs on wavefront 1 (desiredPass above); join: its results are in LDS once everybody has passed this pair of barriers
-  if (lane == 0) forkCmd[0] = 300.0;
-  QM_LDS_BARRIER();
-  QM_LDS_BARRIER();
-
-  QM_TICK(3);
-  // ================================================================== hierarchical QP
-  int status = 0;
-  // x = 0, Z = I
-  for (int e = lane; e < ND * LDZ; e += 64) Z[e] = ((e / LDZ) == (e % LDZ)) ? 1.0 : 0.0;
-  if (lane < ND) xs[lane] = 0.0;
-  // ---- task 0 inequality rows (kept hard, with their slacks, by the lower levels): torque limits + friction pyramid (+ zero rows)
-  const int m0 = 36 + 5 * nst + 3 * nsw;
+}
+// ---- task 0 inequality rows (kept hard, with their slacks, by the lower levels): torque limits + friction pyramid (+ zero rows), m0 in all
+__device__ __forceinline__ void wbcTask0Rows(const qmgpu_model& md, const qmgpu_settings& st, const bool* contact, int m0, const double* M, const double* Jf, const double* nle, double* D0, double* f0, int lane) {
   for (int e = lane; e < MAXM * ND; e += 64) D0[e] = 0.0;
   QM_WAVE_SYNC();
   // WbcBase.cpp:392-415; the LF leg limits are reused for every leg (WbcBase.cpp:599-600).  Rows i and 18 + i = +-[M_joint | -J_joint^T], element by element
@@ -652,13 +558,239 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
     }
     for (int r = 36; r < m0; ++r) f0[r] = 0.0;
   }
+}
+// ---- the equality task A x = b of a level of the cascade (HierarchicalWbc::update / HierarchicalMpcWbc::update: variant 0 / 1); returns its rows r
+__device__ __forceinline__ int wbcAssembleTask(int level, int variant, double time, const qmgpu_settings& st, const bool* contact, int nsw, const double* M, const double* nle, const double* Jf, const double* Ja,
+                                               const double* mi, const double* qM, const double* vM, const double* qD, const double* vD, const double* uDes, double* A, double* bvec, int lane) {
+  for (int e = lane; e < MAXR * ND; e += 64) A[e] = 0.0;
+  QM_WAVE_SYNC();
+  int r = 0;
+  if (level == 0) {
+    r = 18;
+    if (lane < 6) {  // floating-base equations of motion (WbcBase.cpp:370-388)
+      for (int j = 0; j < NVV; ++j) A[lane * ND + j] = M[lane * NVV + j];
+      for (int j = 0; j < 12; ++j) A[lane * ND + 24 + j] = -Jf[j * NVV + lane];
+      bvec[lane] = -nle[lane];
+    }
+    {   // rows of Jacobians are copied by one lane per column (lanes 32..55), the right-hand sides by lane 56
+      const int jc = lane - 32;
+      int row = 6;
+      for (int c = 0; c < 4; ++c) if (contact[c]) {  // no contact motion (WbcBase.cpp:418-433)
+        for (int q = 0; q < 3; ++q) {
+          if (jc >= 0 && jc < NVV) A[(row + q) * ND + jc] = Jf[(3 * c + q) * NVV + jc];
+          if (lane == 56) bvec[row + q] = -mi[MI_FOOTDJV + 3 * c + q];
+        }
+        row += 3;
+      }
+      for (int c = 0; c < 4; ++c) if (!contact[c]) {  // swing feet carry no force (WbcBase.cpp:440-449)
+        if (lane == 56) for (int q = 0; q < 3; ++q) { A[(row + q) * ND + 24 + 3 * c + q] = 1.0; bvec[row + q] = 0.0; }
+        row += 3;
+      }
+    }
+  } else if (level == 1) {
+    const bool startup = variant == 0 && time < 10.0;  // HierarchicalWbc.cpp:32-37
+    if (startup) {
+      r = 6;
+      if (lane < 6) {  // arm joint tracking (WbcBase.cpp:471-497)
+        A[lane * ND + 18 + lane] = 1.0;
+        bvec[lane] = st.kp_arm_joint[lane] * (qD[18 + lane] - qM[18 + lane]) + st.kd_arm_joint[lane] * (vD[18 + lane] - vM[18 + lane]);
+      }
+    } else {
+      const int extra = variant == 0 ? 6 : 2;
+      r = 4 + extra + 3 * nsw;
+      if (lane == 0) {
+        // base height (WbcBase.cpp:308-320)
+        A[2] = 1.0;
+        bvec[0] = mi[MI_BACC + 2] + st.kp_base_height * (qD[2] - qM[2]) + st.kd_base_height * (vD[2] - vM[2]);
+        // base angular (WbcBase.cpp:270-305): Euler maps at the MEASURED angles
+        for (int q = 0; q < 3; ++q) for (int j = 3; j < 6; ++j) A[(1 + q) * ND + j] = mi[MI_BAX + 3 * (j - 3) + q];
+        double sz, cz, sy, cy;
+        sincos(qM[3], &sz, &cz); sincos(qM[4], &sy, &cy);
+        auto omegaOf = [&](const double* de, double* w) { w[0] = -sz * de[1] + cy * cz * de[2]; w[1] = cz * de[1] + cy * sz * de[2]; w[2] = de[0] - sy * de[2]; };
+        double wM[3], wD[3], acc[3];
+        omegaOf(vM + 3, wM); omegaOf(vD + 3, wD);
+        {
+          const double* de = vD + 3; const double* dde = mi + MI_BACC + 3;
+          const double szt = cz * de[0], czt = -sz * de[0], syt = cy * de[1], cyt = -sy * de[1];
+          acc[0] = -sz * dde[1] + cy * cz * dde[2] - szt * de[1] + (cyt * cz + cy * czt) * de[2];
+          acc[1] = cz * dde[1] + cy * sz * dde[2] + czt * de[1] + (cyt * sz + cy * szt) * de[2];
+          acc[2] = dde[0] - sy * dde[2] - syt * de[2];
+        }
+        // rotation error log(R_des R_meas^T)
+        double Rd[9], Rm[9];
+        {
+          double s3, c3, s4, c4, s5, c5;
+          sincos(qD[3], &s3, &c3); sincos(qD[4], &s4, &c4); sincos(qD[5], &s5, &c5);
+          const double t[9] = {c3 * c4, c3 * s4 * s5 - s3 * c5, c3 * s4 * c5 + s3 * s5, s3 * c4, s3 * s4 * s5 + c3 * c5, s3 * s4 * c5 - c3 * s5, -s4, c4 * s5, c4 * c5};
+          for (int i = 0; i < 9; ++i) Rd[i] = t[i];
+          sincos(qM[5], &s5, &c5);
+          const double u[9] = {cz * cy, cz * sy * s5 - sz * c5, cz * sy * c5 + sz * s5, sz * cy, sz * sy * s5 + cz * c5, sz * sy * c5 - cz * s5, -sy, cy * s5, cy * c5};
+          for (int i = 0; i < 9; ++i) Rm[i] = u[i];
+        }
+        auto rotErr = [&](const double* L, const double* Rr, double* e) {
+          double E[9];
+          for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) E[i * 3 + j] = L[i * 3] * Rr[j * 3] + L[i * 3 + 1] * Rr[j * 3 + 1] + L[i * 3 + 2] * Rr[j * 3 + 2];
+          const double tr = E[0] + E[4] + E[8];
+          const double cth = fmax(-1.0, fmin(1.0, 0.5 * (tr - 1.0)));
+          const double th = acos(cth);
+          const double kk = th < 1e-4 ? 0.5 + th * th / 12.0 : 0.5 * th / sin(th);
+          e[0] = kk * (E[7] - E[5]); e[1] = kk * (E[2] - E[6]); e[2] = kk * (E[3] - E[1]);
+        };
+        double err[3];
+        rotErr(Rd, Rm, err);
+        for (int q = 0; q < 3; ++q) bvec[1 + q] = acc[q] + st.kp_base_angular * err[q] + st.kd_base_angular * (wD[q] - wM[q]) - mi[MI_AL0 + q];
+        int row = 4;
+        if (variant == 0) {
+          // end-effector linear (WbcBase.cpp:499-524) and angular (WbcBase.cpp:526-563: columns 3..5 zeroed, desired angular velocity unused)
+          double eerr[3];
+          rotErr(mi + MI_EERD, mi + MI_EERM, eerr);
+          for (int q = 0; q < 3; ++q) {
+            bvec[row + q] = st.kp_ee_linear[q] * (mi[MI_EEPD + q] - mi[MI_EEPM + q]) + st.kd_ee_linear[q] * (mi[MI_EEVD + q] - mi[MI_EEVM + q]) - mi[MI_EEDJL + q];
+            bvec[row + 3 + q] = st.kp_ee_angular[q] * eerr[q] + st.kd_ee_angular[q] * (-mi[MI_EEWM + q]) - mi[MI_EEDJA + q];
+          }
+          row += 6;
+        } else {
+          for (int q = 0; q < 2; ++q) {  // base linear (WbcBase.cpp:240-252)
+            A[(row + q) * ND + q] = 1.0;
+            bvec[row + q] = mi[MI_BACC + q] + st.kp_base_linear * (qD[q] - qM[q]) + st.kd_base_linear * (vD[q] - vM[q]);
+          }
+          row += 2;
+        }
+        for (int c = 0; c < 4; ++c) if (!contact[c]) {  // swing legs, weight 100 (WbcBase.cpp:323-346, HierarchicalWbc.cpp:29)
+          for (int q = 0; q < 3; ++q) {
+            const double acc2 = st.kp_swing * (mi[MI_FOOTPD + 3 * c + q] - mi[MI_FOOTPM + 3 * c + q]) + st.kd_swing * (mi[MI_FOOTVD + 3 * c + q] - mi[MI_FOOTVM + 3 * c + q]);
+            bvec[row + q] = 100.0 * (acc2 - mi[MI_FOOTDJV + 3 * c + q]);
+          }
+          row += 3;
+        }
+      }
+      if (lane >= 32 && lane < 32 + NVV) {   // the Jacobian rows of the same tasks, one lane per column (lane 0 is busy with the right-hand sides)
+        const int j = lane - 32;
+        int row = 4;
+        if (variant == 0) {
+          for (int q = 0; q < 3; ++q) { A[(row + q) * ND + j] = Ja[q * NVV + j]; A[(row + 3 + q) * ND + j] = (j >= 3 && j < 6) ? 0.0 : Ja[(3 + q) * NVV + j]; }
+          row += 6;
+        } else row += 2;
+        for (int c = 0; c < 4; ++c) if (!contact[c]) {
+          for (int q = 0; q < 3; ++q) A[(row + q) * ND + j] = 100.0 * Jf[(3 * c + q) * NVV + j];
+          row += 3;
+        }
+      }
+    }
+  } else {
+    r = variant == 0 ? 14 : 12;
+    if (lane < 12) { A[lane * ND + 24 + lane] = 1.0; bvec[lane] = uDes[lane]; }  // contact forces (WbcBase.cpp:566-578)
+    if (variant == 0 && lane >= 12 && lane < 14) {  // base linear (WbcBase.cpp:240-252)
+      const int q = lane - 12;
+      A[lane * ND + q] = 1.0;
+      bvec[lane] = mi[MI_BACC + q] + st.kp_base_linear * (qD[q] - qM[q]) + st.kd_base_linear * (vD[q] - vM[q]);
+    }
+  }
+  return r;
+}
+// ---- updateCmd (WbcBase.cpp:580-595): tau = [M_j, -J_j^T] x + h_j
+__device__ __forceinline__ void wbcUpdateCmd(const WbcArgs& a, int inst, int status, const double* xs, const double* nle, const double* M, const double* Jf, int lane) {
+  if (lane < ND) a.out[size_t(inst) * 54 + lane] = xs[lane];
+  if (lane < 18) {
+    double s = nle[6 + lane];
+    for (int j = 0; j < NVV; ++j) s += M[(6 + lane) * NVV + j] * xs[j];
+    for (int j = 0; j < 12; ++j) s -= Jf[j * NVV + 6 + lane] * xs[24 + j];
+    a.out[size_t(inst) * 54 + 36 + lane] = s;
+  }
+  if (lane == 0 && a.status) a.status[inst] = status;
+}
+
+__global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(WbcArgs a) {
+  QM_DYNAMIC_LDS(lds);
+#if defined(QM_WBC_OPAQUE_LDS) && !defined(QMGPU_HOST_EMULATION)
+  // Build variant (tools/wbc_variants.py, DESIGN.md section 4.7): the arrays of the carve are addressed through one opaque address-space-3 base
+  // register (round 2: wrong torques with IPRA on, correct with it off).
+  QM_OPAQUE_LDS(double, ldsO, lds);
+  double* carve = (double*)ldsO;
+#else
+  double* carve = lds;
+#endif
+  QM_POISON_LDS(lds, WBC_LDS_DOUBLES);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, inst = blockIdx.x;
+  // (the model constants reach this kernel through ~800 vector loads per instance -- after its first global store a kernel cannot use scalar loads for them,
+  //  gpu_rt.h: QM_CONSTANT_REF; a copy of the struct in LDS was measured in round 3 and not kept: 0.4405 -> 0.4445 ms, the loads are batched well enough)
+  const qmgpu_model& md = a.P->model;
+  const qmgpu_settings& st = a.P->settings;
+  double fe[3] = {0.0, 0.0, 0.0};   // external force on the arm end-effector (force tracking; zero otherwise)
+  if (a.eeForce) for (int i = 0; i < 3; ++i) fe[i] = a.eeForce[size_t(inst) * 3 + i];
+  double* in = carve + WL_IN.off; double* rbd = in + IN_RBD; double* xDes = in + IN_XDES; double* uDes = in + IN_UDES; double* il = in + IN_LAST;
+  double* qM = carve + WL_Q.off; double* vM = qM + NVV; double* qD = qM + 2 * NVV; double* vD = qM + 3 * NVV;
+  double* body = carve + WL_BODY.off; double* dof = carve + WL_DOF.off; double* wr = carve + WL_WR.off; double* M = carve + WL_M.off; double* nle = carve + WL_NLE.off;
+  double* Jf = carve + WL_JF.off; double* Ja = carve + WL_JA.off; double* mi = carve + WL_MISC.off;
+  double* A = carve + WL_A.off; double* bvec = carve + WL_B.off; double* D0 = carve + WL_D0.off; double* f0 = carve + WL_F0.off; double* v0 = carve + WL_V0.off;
+  double* Z = carve + WL_Z.off; double* Zn = carve + WL_ZN.off; double* AZ = carve + WL_AZ.off; double* DZ = carve + WL_DZ.off; double* K = carve + WL_K.off; double* G = carve + WL_G.off;
+  double* xs = carve + WL_X.off; double* zs = carve + WL_ZS.off; double* rds = carve + WL_RD.off; double* dzs = carve + WL_DZS.off;
+  double* fhat = carve + WL_FHAT.off; double* tzv = carve + WL_TZ.off; double* red = carve + WL_RED.off;
+
+  // Wavefront 0 solves the instance; the other three sit on the CU's idle SIMDs and take their share of the matrix-core tiles of the
+  // interior point between two workgroup barriers (ipmKTiles).  Command word: forkCmd[0] (FORK_LEAVE = leave).
+  double* forkCmd = carve + WL_CTL.off + CTL_FORK; double* forkJob = red + WX_FORKJOB.off;
+  if (wave != 0) {
+    QM_LDS_BARRIER();                                     // inputs and coordinates (S1, S2) are in LDS
+    if (wave == 1) wbcDesiredPass(md, st, xDes, uDes, fe, qD, vD, mi, lds + WL_BODY2.off, lds + WL_DOF2.off, lane);   // S5
+    wbcHelperLoop(lds, carve, forkCmd, forkJob, wave, lane);
+    return;
+  }
+  // C (M x N, LDS) = op(A) B with the four wavefronts sharing the tiles
+  auto forkGemm = [&](bool ta, const double* jA, int lda, const double* jB, int ldb, int jM, int jN, int jK, double* jD, int ldd, double diagAdd) {
+    if (lane == 0) {
+      forkJob[FJ_A] = double(jA - lds); forkJob[FJ_LDA] = lda; forkJob[FJ_B] = double(jB - lds); forkJob[FJ_LDB] = ldb; forkJob[FJ_M] = jM; forkJob[FJ_N] = jN; forkJob[FJ_K] = jK;
+      forkJob[FJ_D] = double(jD - lds); forkJob[FJ_LDD] = ldd; forkJob[FJ_DIAG] = diagAdd; forkCmd[0] = ta ? double(FORK_GEMM_T) : double(FORK_GEMM);
+    }
+    QM_LDS_BARRIER();
+    if (ta) waveGemmTiles<true>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, diagAdd, 0, lane);
+    else waveGemmTiles<false>(jA, lda, jB, ldb, jM, jN, jK, jD, ldd, diagAdd, 0, lane);
+    QM_LDS_BARRIER();
+  };
+  const int mode = a.mode[inst];
+  const double period = a.period[inst], time = a.time[inst];
+  bool contact[4]; int nst = 0;
+  for (int c = 0; c < 4; ++c) { contact[c] = contactOf(mode, c); nst += contact[c] ? 1 : 0; }
+  const int nsw = 4 - nst;
+
+  for (int e = lane; e < MAXM * LDZ; e += 64) DZ[e] = 0.0;  // rows >= m0 are never written: the interior point only needs them finite
+  QM_TICK_DECL;
+#ifdef QM_RICCATI_TIMING
+  const unsigned long long qmStart = clock64();
+#endif
+  wbcLoadInputs(a, inst, rbd, xDes, uDes, il, lane);                                    // S1
+  QM_WAVE_SYNC();
+  wbcCoordinates(rbd, xDes, uDes, il, period, qM, vM, qD, vD, mi, lane);                // S2
+  if (lane < 30) a.inputLast[size_t(inst) * 30 + lane] = uDes[lane];  // WbcBase.cpp:225
+  QM_LDS_BARRIER();      // wavefront 1 starts the desired pass (S5) from here
+
+  QM_TICK(0);
+  wbcMeasuredPass(md, st, qM, vM, body, dof, wr, lane);                                 // S3
+  QM_WAVE_SYNC();
+  QM_TICK(1);
+  double* JL = carve + WO_JL.off;   // [19][24][6] over Z, Z_new and the head of A Z (all unused before the first level)
+  wbcInertiaAndJacobians(md, fe, body, dof, wr, JL, M, nle, Jf, Ja, mi, lane);          // S4
+  QM_WAVE_SYNC();
+
+  QM_TICK(2);
+  // ---- S5 runs on wavefront 1 (wbcDesiredPass); join: its results are in LDS once everybody has passed this pair of barriers
+  if (lane == 0) forkCmd[0] = double(FORK_JOIN);
+  QM_LDS_BARRIER();
+  QM_LDS_BARRIER();
+
+  QM_TICK(3);
+  // ================================================================== hierarchical QP
+  int status = 0;
+  // x = 0, Z = I
+  for (int e = lane; e < ND * LDZ; e += 64) Z[e] = ((e / LDZ) == (e % LDZ)) ? 1.0 : 0.0;
+  if (lane < ND) xs[lane] = 0.0;
+  const int m0 = 36 + 5 * nst + 3 * nsw;
+  wbcTask0Rows(md, st, contact, m0, M, Jf, nle, D0, f0, lane);
   QM_WAVE_SYNC();
 
   // scratch of the implied-equality step: the body / wrench tables of the model update are free by now (the desired pass has joined)
-  double* scrA = lds + W_BODY;       // 904 doubles: W_BODY | W_DOF | W_WR
-  double* scrB = lds + W_BODY2;      // 784 doubles: W_BODY2 | W_DOF2
-  static_assert(W_DOF == W_BODY + 640 && W_WR == W_DOF + 144 && W_M == W_WR + 120 && 24 * LDZ <= 904 && MAXR * LDZ <= 904 && 18 * LDZ <= 784, "scratch regions of the implied-equality step");
-  static_assert(QP_KMAX * QP_SLD <= MAXR * 40, "the small system of the pinned rows fits the table region");
+  double* scrA = lds + WO_SCRA.off;
+  double* scrB = lds + WO_SCRB.off;
   // rows of `cnt` x n  <-  rows N_E (N_E: n x nE in K), in place, 24 rows at a time through scrA; columns >= nE cleared
   auto rightMultiply = [&](double* rowsP, int cnt, int n, int nE) {
 #pragma unroll 1
@@ -670,14 +802,15 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
       QM_WAVE_SYNC();
     }
   };
-  // The QP of one level (or of its canonical representative) in nVars variables: task rows AZp (rRows x nVars) with residual rhatp at z = 0, inequality rows DZ / fhat
+  // The QP of one level (or of its canonical representative) in nVars variables: task rows AZp (rRows x nVars, at offset azOff of the carve) with residual rhatp (at rhatOff) at z = 0, inequality rows DZ / fhat
   // (own: the level's own, soft; else inherited, hard).  Rows a higher level left strongly active (eqIn) are equalities here: removed exactly by the change of variables
   // z = N_E w (N_E = kernel of those rows; DESIGN.md section 4.7 has the argument), the QP is solved in w.  Result: z in zs[0 .. nVars);
   // strongOut: this lane's row is strongly active at the solution; returns the solver's status.  AZp and DZ are overwritten when rows are eliminated.
   // warmIo (in / out): the word of this solve in the instance's working-set record (0: none / cold); passes gets bit 7 when the carried guess was refuted.
   // warmZ (global memory or null): where the solution of this solve travels with its rows (bit 62 of the word; not when implied equalities changed the variables).
   // regular: a level's own solve (HoQp's regulariser applies: kept literally where qp_dev.h's `lit` says), not the canonical representative's.
-  auto levelQp = [&](double* AZp, int rRows, double* rhatp, int nVars, bool own, bool rowOnIn, bool eqIn, bool& strongOut, int& passes, unsigned long long& warmIo, double* warmZ, bool regular) -> int {
+  auto levelQp = [&](int azOff, int rRows, int rhatOff, int nVars, bool own, bool rowOnIn, bool eqIn, bool& strongOut, int& passes, unsigned long long& warmIo, double* warmZ, bool regular) -> int {
+    double* AZp = lds + azOff; double* rhatp = lds + rhatOff;
     int nQ = nVars;
     bool rowOn = rowOnIn, reduced = false;
     strongOut = false;
@@ -692,7 +825,7 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
         const int kE = qmPopCount(eqMask) < MAXR ? qmPopCount(eqMask) : MAXR;
         if (mineE) for (int j = 0; j < LDZ; ++j) scrA[slotE * LDZ + j] = j < nVars ? DZ[lane * LDZ + j] : 0.0;
         QM_WAVE_SYNC();
-        nQ = wbcNullSpace(int(scrA - lds), kE, nVars, int(K - lds), int(Vh - lds), int(red - lds), lane);
+        nQ = wbcNullSpace(WO_SCRA.off, kE, nVars, WL_K.off, WL_RED.off, lane);
         if (nQ == 0) { if (lane < ND) zs[lane] = 0.0; QM_WAVE_SYNC(); return 0; }     // the equalities leave nothing to decide
         for (int e = lane; e < nVars * LDZ; e += 64) { const int i = e / LDZ, j = e - i * LDZ; scrB[e] = j < nQ ? K[i * LDK + j] : 0.0; }     // N_E survives the solve in scrB
         double dnOld = 0.0, dnNew = 0.0;
@@ -716,7 +849,7 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
     if (own && rRows <= nQ && rRows <= MAXR) {
       double winv = 1.0;
       if (lane < nQ) for (int i = 0; i < m0; ++i) if (fhat[i] == 0.0 && DZ[i * LDZ + lane] != 0.0) winv = 1e4;
-      // B = W^-1 (A Z)' (n x r) in Zn (free until the level's null space), then (A Z) B on the matrix cores into K
+      // B = W^-1 (A Z)' (n x r) in Zn (WO_MNB: free until the level's null space), then (A Z) B on the matrix cores into K
       for (int e = lane; e < nQ * rRows; e += 64) { const int c = e / rRows, j = e - c * rRows; Zn[c * LDZ + j] = AZp[j * LDZ + c]; }
       QM_WAVE_SYNC();
       if (lane < nQ) for (int j = 0; j < rRows; ++j) Zn[lane * LDZ + j] *= winv;
@@ -767,7 +900,7 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
     QM_WAVE_SYNC();
     forkGemm(true, AZp, LDZ, AZp, LDZ, nQ, nQ, rRows, G, LDK, 0.0);
     QM_WAVE_SYNC();
-    const QpOff io{int(G - lds), int(AZp - lds), int(rhatp - lds), int(DZ - lds), int(fhat - lds), int(K - lds), int(wt - lds), int(zs - lds), int(red - lds), int(forkCmd - lds), int(Vh - lds), W_TP};
+    const QpOff io = qpOffOf(azOff, rhatOff);
     auto solve = [&](bool tryHeld, bool ownIpm) {
       QpResult rr;
       const double sigma0 = ownIpm ? 0.5 : ((own || nQ <= 8) ? -1.0 : 0.5);         // (small levels go without the interior point: cold, the active-set method is shorter there in mean and in the tail)
@@ -847,130 +980,7 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
     if (n == 0) break;  // FLY: nothing left to decide
     QM_TICK(4);
     // ---- assemble this level's equality task A x = b  (rows r)
-    for (int e = lane; e < MAXR * ND; e += 64) A[e] = 0.0;
-    QM_WAVE_SYNC();
-    int r = 0;
-    if (level == 0) {
-      r = 18;
-      if (lane < 6) {  // floating-base equations of motion (WbcBase.cpp:370-388)
-        for (int j = 0; j < NVV; ++j) A[lane * ND + j] = M[lane * NVV + j];
-        for (int j = 0; j < 12; ++j) A[lane * ND + 24 + j] = -Jf[j * NVV + lane];
-        bvec[lane] = -nle[lane];
-      }
-      {   // rows of Jacobians are copied by one lane per column (lanes 32..55), the right-hand sides by lane 56
-        const int jc = lane - 32;
-        int row = 6;
-        for (int c = 0; c < 4; ++c) if (contact[c]) {  // no contact motion (WbcBase.cpp:418-433)
-          for (int q = 0; q < 3; ++q) {
-            if (jc >= 0 && jc < NVV) A[(row + q) * ND + jc] = Jf[(3 * c + q) * NVV + jc];
-            if (lane == 56) bvec[row + q] = -mi[MI_FOOTDJV + 3 * c + q];
-          }
-          row += 3;
-        }
-        for (int c = 0; c < 4; ++c) if (!contact[c]) {  // swing feet carry no force (WbcBase.cpp:440-449)
-          if (lane == 56) for (int q = 0; q < 3; ++q) { A[(row + q) * ND + 24 + 3 * c + q] = 1.0; bvec[row + q] = 0.0; }
-          row += 3;
-        }
-      }
-    } else if (level == 1) {
-      const bool startup = a.variant == 0 && time < 10.0;  // HierarchicalWbc.cpp:32-37
-      if (startup) {
-        r = 6;
-        if (lane < 6) {  // arm joint tracking (WbcBase.cpp:471-497)
-          A[lane * ND + 18 + lane] = 1.0;
-          bvec[lane] = st.kp_arm_joint[lane] * (qD[18 + lane] - qM[18 + lane]) + st.kd_arm_joint[lane] * (vD[18 + lane] - vM[18 + lane]);
-        }
-      } else {
-        const int extra = a.variant == 0 ? 6 : 2;
-        r = 4 + extra + 3 * nsw;
-        if (lane == 0) {
-          // base height (WbcBase.cpp:308-320)
-          A[2] = 1.0;
-          bvec[0] = mi[MI_BACC + 2] + st.kp_base_height * (qD[2] - qM[2]) + st.kd_base_height * (vD[2] - vM[2]);
-          // base angular (WbcBase.cpp:270-305): Euler maps at the MEASURED angles
-          for (int q = 0; q < 3; ++q) for (int j = 3; j < 6; ++j) A[(1 + q) * ND + j] = mi[MI_BAX + 3 * (j - 3) + q];
-          double sz, cz, sy, cy;
-          sincos(qM[3], &sz, &cz); sincos(qM[4], &sy, &cy);
-          auto omegaOf = [&](const double* de, double* w) { w[0] = -sz * de[1] + cy * cz * de[2]; w[1] = cz * de[1] + cy * sz * de[2]; w[2] = de[0] - sy * de[2]; };
-          double wM[3], wD[3], acc[3];
-          omegaOf(vM + 3, wM); omegaOf(vD + 3, wD);
-          {
-            const double* de = vD + 3; const double* dde = mi + MI_BACC + 3;
-            const double szt = cz * de[0], czt = -sz * de[0], syt = cy * de[1], cyt = -sy * de[1];
-            acc[0] = -sz * dde[1] + cy * cz * dde[2] - szt * de[1] + (cyt * cz + cy * czt) * de[2];
-            acc[1] = cz * dde[1] + cy * sz * dde[2] + czt * de[1] + (cyt * sz + cy * szt) * de[2];
-            acc[2] = dde[0] - sy * dde[2] - syt * de[2];
-          }
-          // rotation error log(R_des R_meas^T)
-          double Rd[9], Rm[9];
-          {
-            double s3, c3, s4, c4, s5, c5;
-            sincos(qD[3], &s3, &c3); sincos(qD[4], &s4, &c4); sincos(qD[5], &s5, &c5);
-            const double t[9] = {c3 * c4, c3 * s4 * s5 - s3 * c5, c3 * s4 * c5 + s3 * s5, s3 * c4, s3 * s4 * s5 + c3 * c5, s3 * s4 * c5 - c3 * s5, -s4, c4 * s5, c4 * c5};
-            for (int i = 0; i < 9; ++i) Rd[i] = t[i];
-            sincos(qM[5], &s5, &c5);
-            const double u[9] = {cz * cy, cz * sy * s5 - sz * c5, cz * sy * c5 + sz * s5, sz * cy, sz * sy * s5 + cz * c5, sz * sy * c5 - cz * s5, -sy, cy * s5, cy * c5};
-            for (int i = 0; i < 9; ++i) Rm[i] = u[i];
-          }
-          auto rotErr = [&](const double* L, const double* Rr, double* e) {
-            double E[9];
-            for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) E[i * 3 + j] = L[i * 3] * Rr[j * 3] + L[i * 3 + 1] * Rr[j * 3 + 1] + L[i * 3 + 2] * Rr[j * 3 + 2];
-            const double tr = E[0] + E[4] + E[8];
-            const double cth = fmax(-1.0, fmin(1.0, 0.5 * (tr - 1.0)));
-            const double th = acos(cth);
-            const double kk = th < 1e-4 ? 0.5 + th * th / 12.0 : 0.5 * th / sin(th);
-            e[0] = kk * (E[7] - E[5]); e[1] = kk * (E[2] - E[6]); e[2] = kk * (E[3] - E[1]);
-          };
-          double err[3];
-          rotErr(Rd, Rm, err);
-          for (int q = 0; q < 3; ++q) bvec[1 + q] = acc[q] + st.kp_base_angular * err[q] + st.kd_base_angular * (wD[q] - wM[q]) - mi[MI_AL0 + q];
-          int row = 4;
-          if (a.variant == 0) {
-            // end-effector linear (WbcBase.cpp:499-524) and angular (WbcBase.cpp:526-563: columns 3..5 zeroed, desired angular velocity unused)
-            double eerr[3];
-            rotErr(mi + MI_EERD, mi + MI_EERM, eerr);
-            for (int q = 0; q < 3; ++q) {
-              bvec[row + q] = st.kp_ee_linear[q] * (mi[MI_EEPD + q] - mi[MI_EEPM + q]) + st.kd_ee_linear[q] * (mi[MI_EEVD + q] - mi[MI_EEVM + q]) - mi[MI_EEDJL + q];
-              bvec[row + 3 + q] = st.kp_ee_angular[q] * eerr[q] + st.kd_ee_angular[q] * (-mi[MI_EEWM + q]) - mi[MI_EEDJA + q];
-            }
-            row += 6;
-          } else {
-            for (int q = 0; q < 2; ++q) {  // base linear (WbcBase.cpp:240-252)
-              A[(row + q) * ND + q] = 1.0;
-              bvec[row + q] = mi[MI_BACC + q] + st.kp_base_linear * (qD[q] - qM[q]) + st.kd_base_linear * (vD[q] - vM[q]);
-            }
-            row += 2;
-          }
-          for (int c = 0; c < 4; ++c) if (!contact[c]) {  // swing legs, weight 100 (WbcBase.cpp:323-346, HierarchicalWbc.cpp:29)
-            for (int q = 0; q < 3; ++q) {
-              const double acc2 = st.kp_swing * (mi[MI_FOOTPD + 3 * c + q] - mi[MI_FOOTPM + 3 * c + q]) + st.kd_swing * (mi[MI_FOOTVD + 3 * c + q] - mi[MI_FOOTVM + 3 * c + q]);
-              bvec[row + q] = 100.0 * (acc2 - mi[MI_FOOTDJV + 3 * c + q]);
-            }
-            row += 3;
-          }
-        }
-        if (lane >= 32 && lane < 32 + NVV) {   // the Jacobian rows of the same tasks, one lane per column (lane 0 is busy with the right-hand sides)
-          const int j = lane - 32;
-          int row = 4;
-          if (a.variant == 0) {
-            for (int q = 0; q < 3; ++q) { A[(row + q) * ND + j] = Ja[q * NVV + j]; A[(row + 3 + q) * ND + j] = (j >= 3 && j < 6) ? 0.0 : Ja[(3 + q) * NVV + j]; }
-            row += 6;
-          } else row += 2;
-          for (int c = 0; c < 4; ++c) if (!contact[c]) {
-            for (int q = 0; q < 3; ++q) A[(row + q) * ND + j] = 100.0 * Jf[(3 * c + q) * NVV + j];
-            row += 3;
-          }
-        }
-      }
-    } else {
-      r = a.variant == 0 ? 14 : 12;
-      if (lane < 12) { A[lane * ND + 24 + lane] = 1.0; bvec[lane] = uDes[lane]; }  // contact forces (WbcBase.cpp:566-578)
-      if (a.variant == 0 && lane >= 12 && lane < 14) {  // base linear (WbcBase.cpp:240-252)
-        const int q = lane - 12;
-        A[lane * ND + q] = 1.0;
-        bvec[lane] = mi[MI_BACC + q] + st.kp_base_linear * (qD[q] - qM[q]) + st.kd_base_linear * (vD[q] - vM[q]);
-      }
-    }
+    const int r = wbcAssembleTask(level, a.variant, time, st, contact, nsw, M, nle, Jf, Ja, mi, qM, vM, qD, vD, uDes, A, bvec, lane);
     QM_WAVE_SYNC();
 
     QM_TICK(5);
@@ -993,7 +1003,7 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
     unsigned long long wsWord = wsLoad(pass, level, 0);
     // (words 16..33 / 34..41 of the record: the solutions of the second and third level of pass 0)
     double* wsZ = (wsRec && pass == 0 && ((level == 1 && n <= 18) || (level == 2 && n <= 8))) ? reinterpret_cast<double*>(wsRec + (level == 1 ? 16 : 34)) : nullptr;
-    const int st = levelQp(AZ, r, tzv, n, level == 0, rowNonZero(n), eqRow, strong, passes, wsWord, wsZ, true);
+    const int st = levelQp(WL_AZ.off, r, WL_TZ.off, n, level == 0, rowNonZero(n), eqRow, strong, passes, wsWord, wsZ, true);
     wsStore(pass, level, 0, wsWord, passes);
     eqRow = eqRow || strong;
     if (st != 0) status |= (1 << level);
@@ -1014,7 +1024,7 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
     // ---- Z <- Z kernel(A Z) (HoQp.cpp:126-133); A Z again where the implied equalities overwrote it
     if (hadEq) { for (int e = lane; e < MAXR * LDZ; e += 64) AZ[e] = 0.0; QM_WAVE_SYNC(); forkGemm(false, A, ND, Z, LDZ, r, n, ND, AZ, LDZ, 0.0); QM_WAVE_SYNC(); }
     const int nOld = n;
-    const int nNew = wbcNullSpace(int(AZ - lds), r, n, int(K - lds), int(Vh - lds), int(red - lds), lane);
+    const int nNew = wbcNullSpace(WL_AZ.off, r, n, WL_K.off, WL_RED.off, lane);
     QM_TICK(16);
     // Z N on the matrix cores (columns >= n of Z are zero, rows >= n of N too)
     forkGemm(false, Z, LDZ, K, LDK, ND, nNew, n, Zn, LDZ, 0.0);
@@ -1043,7 +1053,7 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
     QM_TICK(17);
     // ---- canonical representative of the level (pass 1): min |z* + N w|^2 inside the inequality rows, i.e. task rows N (nOld x n), residual z* (rds); x += Z w
     if (canonical && n > 0) {
-      double* AZc = level == 0 ? Zn : AZ;
+      const int azcOff = level == 0 ? WL_ZN.off : WL_AZ.off;
       if (level == 0) { for (int e = lane; e < ND * LDZ; e += 64) { const int j = e % LDZ; if (j >= n) Zn[e] = 0.0; } }
       for (int e = lane; e < MAXM * LDZ; e += 64) DZ[e] = 0.0;
       QM_WAVE_SYNC();
@@ -1052,7 +1062,7 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
       QM_WAVE_SYNC();
       bool strongC = false; int passesC = 0;
       unsigned long long wsWordC = wsLoad(pass, level, 1);
-      const int stc = levelQp(AZc, nOld, rds, n, false, rowNonZero(n), eqRow, strongC, passesC, wsWordC, nullptr, false);
+      const int stc = levelQp(azcOff, nOld, WL_RD.off, n, false, rowNonZero(n), eqRow, strongC, passesC, wsWordC, nullptr, false);
       wsStore(pass, level, 1, wsWordC, passesC);
       if (stc != 0) status |= 8;
       double xc = 0.0;
@@ -1067,17 +1077,9 @@ __global__ void __launch_bounds__(WBC_THREADS) QM_ONE_WAVE_PER_SIMD wbc_kernel(W
   }
   QM_WAVE_SYNC();
   QM_TICK(9);
-  // ---- updateCmd (WbcBase.cpp:580-595): tau = [M_j, -J_j^T] x + h_j
-  if (lane < ND) a.out[size_t(inst) * 54 + lane] = xs[lane];
-  if (lane < 18) {
-    double s = nle[6 + lane];
-    for (int j = 0; j < NVV; ++j) s += M[(6 + lane) * NVV + j] * xs[j];
-    for (int j = 0; j < 12; ++j) s -= Jf[j * NVV + 6 + lane] * xs[24 + j];
-    a.out[size_t(inst) * 54 + 36 + lane] = s;
-  }
-  if (lane == 0 && a.status) a.status[inst] = status;
+  wbcUpdateCmd(a, inst, status, xs, nle, M, Jf, lane);
   if (wsRec && lane == 0) { wsRec[13] = wsCount[0]; wsRec[14] = wsCount[1]; }
-  forkCmd[0] = 0.0;      // release the helper wavefronts
+  forkCmd[0] = double(FORK_LEAVE);      // release the helper wavefronts
   QM_LDS_BARRIER();
   QM_TICK(10);
   QM_TICK_FLUSH(192, blockIdx.x == 0 && lane == 0);

@@ -22,7 +22,7 @@ constexpr int OFF_DTNEXT = OFF_DTPREV + 1;   // (backward / forward order) arriv
 constexpr int OFF_TAIL = OFF_rt + MT + 2;    // end of what the backward sweep reads (3284)
 // The joint rows (12..29) of the projected dynamics are not data of their own: x_j+ = x_j + dt v_j exactly, so
 //   A~[i][:] = e_i + dt Px[i][:],   B~[i][:] = dt Pu[i][:]      (i >= 12; du = Pe + Px dx + Pu du~)
-// and the record holds Px / Pu THERE, once; riccati_kernel forms the A~ / B~ rows while the staged copy lands in LDS (jointRowsToDynamics).
+// and the record holds Px / Pu THERE, once; riccati_kernel forms the A~ / B~ rows while the staged copy lands in LDS (StagePrefetch::commitDynamics, jointRowMask).
 // Rows 0..11 (force inputs) of Px are structurally zero and rows 0..11 of Pu are unit vectors on the free stance forces in foot order (zero rows for a swing
 // foot, whose force Pe pins): neither exists in the record; the consumers form them from the node's contact mode, which rides in the record's tail.
 // 6.9 + 1.7 KB per stage less written by lq_node_kernel and less read by the forward sweep than with separate A~ B~ / Px Pu copies (round 3).

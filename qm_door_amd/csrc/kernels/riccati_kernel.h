@@ -24,6 +24,7 @@
 #pragma once
 #include "layout.h"
 #include "gpu_rt.h"
+#include "riccati_lds.h"
 
 namespace qmk {
 
@@ -43,30 +44,7 @@ struct RiccatiArgs {
 
 constexpr int RICCATI_WAVES = 4;
 // Phase clocks of the profiling build: QM_TICK* (gpu_rt.h; tools/riccati_phase_probe.py, -DQM_RICCATI_TIMING).  Nothing in the product build.
-// LDS strides (doubles) = 16 mod 32: the four k-rows x sixteen consecutive columns one MFMA operand read touches hit distinct banks
-constexpr int LDS_S = 50, LDS_Y = 80, LDS_W = 48, LDS_TS = 34, LDS_LL = 18;   // LDS_LL / LDS_S: sixteen lanes one row apart (144 / 400 B) hit distinct banks: column walks are as conflict free as row walks
-constexpr int STG_B = OFF_TAIL + 4;               // doubles of a record the backward sweep needs (padded)
-constexpr int STG_F = STAGE_DOUBLES + GAIN_DOUBLES;  // record + gains of one stage for the forward sweep
-constexpr int R_STG = 0;                          // two staging buffers: [2][STG_B] backward, [2][STG_F] forward (over Y / T, dead by then)
-constexpr int R_Y = R_STG + 2 * STG_B;            // Y [32][LDS_Y]
-constexpr int R_T = R_Y + 32 * LDS_Y;             // T [32][LDS_Y]
-constexpr int R_S = R_T + 32 * LDS_Y;             // S [32][LDS_S]
-constexpr int W_DOUBLES = 20 * LDS_W;             // W [20][LDS_W] of one stage
-constexpr int LT_DOUBLES = 20 * LDS_LL;            // L [20][LDS_LL] row major, lower triangle; the diagonal slot holds L_cc out of the factorisation and 1 / L_cc from the stage's P6b on (riccatiInvertDiagonal)
-constexpr int R_W = R_S + 32 * LDS_S;              // W of the stage in flight and of the previous one (by stage parity): the gains of stage k + 1 are
-constexpr int R_LT = R_W + 2 * W_DOUBLES;         // formed while stage k factorises, from W / L^T of stage k + 1
-constexpr int R_KST = R_LT + 2 * LT_DOUBLES;        // the gains record [GAIN_DOUBLES] of two stages: formed here by one wavefront, copied to HBM by two others a stage later
-constexpr int R_SYM = R_KST + 2 * GAIN_DOUBLES;     // [32][LDS_TS] scratch of the wavefront-local symmetrisation (T is being read by the factorisation at that time)
-constexpr int R_Y2 = R_SYM + 32 * LDS_TS;            // [16][LDS_Y] second half of the k sum of Y rows 16..31 when only three column tiles exist (P1 below)
-constexpr int R_BWD_END = R_Y2 + 16 * LDS_Y;
-static_assert(R_KST % 2 == 0 && GAIN_DOUBLES % 2 == 0, "16-byte copies");
-// forward sweep (over everything above, dead by then): a ring of three staging buffers [3][STG_F], then the B-operand images of dx and du~
-constexpr int FWD_ZV = 80;                             // z = [dx (30) | du~ (MT) | Px dx + Pu du~ of the joint rows (30, entries 12..29 used) | 2] of one stage
-constexpr int F_ZV = 3 * STG_F, R_FWD_END = F_ZV + 3 * FWD_ZV;
-constexpr int R_SCR = R_BWD_END > R_FWD_END ? R_BWD_END : R_FWD_END;   // armijo reduction [64]
-constexpr int RICCATI_LDS_DOUBLES = R_SCR + 64;
-constexpr int RICCATI_LDS_BYTES = RICCATI_LDS_DOUBLES * int(sizeof(real));  // ~145 KiB at fp64 (dynamic LDS)
-static_assert(RICCATI_LDS_DOUBLES <= 20480, "one CU's LDS at fp64");
+// (the LDS carve, its strides and overlays: riccati_lds.h)
 
 // Register-staged HBM -> LDS copy for a whole workgroup: issue() puts PF 16-byte loads per thread in flight, commit() drains
 // them into LDS.  Between the two the workgroup computes on the *current* stage, so the memory latency of the next stage is
@@ -191,8 +169,8 @@ template <int NT> __device__ __forceinline__ void riccatiFactorise(const real* T
     inv = qmRsqrtPos(fmax(piv, REAL_PIVOT_MIN));
   }
   // every lane streams its finished rows out as the elimination goes: H lane c writes row c of L (entries right of the diagonal are
-  // elimination residue and never read), G lane c column c of W, the idle lanes a scratch word (row 19 of L)
-  real* out = isH ? LL + c * LDS_LL : (isG ? W + c : LL + 19 * LDS_LL);
+  // elimination residue and never read), G lane c column c of W, the idle lanes a scratch word (a spare row of L: L_SINK_ROW)
+  real* out = isH ? LL + c * LDS_LL : (isG ? W + c : LL + L_SINK_ROW * LDS_LL);
   const int ostr = isH ? 1 : (isG ? LDS_W : 0);
   RiccatiStep<NT, 0>::run(col, inv, bcP, ncP, status, out, ostr);
 #ifdef QM_RICCATI_TIMING
@@ -278,6 +256,38 @@ __device__ __forceinline__ void riccatiGainsOut(const real* kst, real* gain, int
   for (int i = 0; i < (GAIN_DOUBLES / 2 + 127) / 128; ++i) { const int idx = t + 128 * i; if (idx < GAIN_DOUBLES / 2) dst[idx] = src[idx]; }
 }
 
+// ---- terminal value function S_N = Q_N, s_N = q_N (zero padded), the zero fills, and the first stage to process
+template <int NTHR> __device__ __forceinline__ void riccatiPrologue(real* lds, const real* stagesI, const real* dtI, int N, int tid) {
+  constexpr int PFB = (OFF_TAIL / 2 + NTHR - 1) / NTHR;
+  real* S = lds + RL_S.off;
+  const real* rec = stagesI + size_t(N) * STAGE_DOUBLES;
+  // ONE memory round trip for the whole prologue: the record of stage N - 1 is requested first, the terminal Q_N with s_N = q_N as its row 30 (the B operands
+  // carry a unit entry at (30, 30)) behind it, and nothing is waited for before all of them are on their way (were three round trips and a barrier in a row: Q_N,
+  // then q_N into the row the first pass had zeroed, then the record)
+  StagePrefetch<PFB, NTHR> pf;
+  pf.issue(stagesI + size_t(N - 1) * STAGE_DOUBLES, OFF_TAIL, tid);
+  const real dtLast = dtI[N - 1];
+  {   // all of a thread's loads before its first LDS store (a load may not pass the store in front of it: seven memory round trips in a row otherwise)
+    constexpr int NS = (32 * LDS_S + NTHR - 1) / NTHR;
+    real sv[NS];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) {
+      const int e = tid + q * NTHR, i = e / LDS_S, j = e % LDS_S;
+      const bool inQ = e < 32 * LDS_S && i < 30 && j < 30, inq = e < 32 * LDS_S && i == 30 && j < 30;
+      sv[q] = (inQ || inq) ? rec[inq ? OFF_qt + j : OFF_QT + i * 30 + j] : 0.0_r;
+    }
+#pragma unroll
+    for (int q = 0; q < NS; ++q) QM_KEEP(sv[q]);
+#pragma unroll
+    for (int q = 0; q < NS; ++q) { const int e = tid + q * NTHR; if (e < 32 * LDS_S) S[e] = sv[q]; }
+  }
+  for (int e = tid; e < RL_FILL_WLK.count; e += NTHR) lds[RL_FILL_WLK.off + e] = 0.0_r;   // W, L, gains images of both parities
+  real* yt = lds + RL_FILL_YT.off;
+  for (int e = tid; e < RL_FILL_YT.count; e += NTHR) yt[e] = 0.0_r;     // Y, T
+  for (int e = tid; e < RL_Y2.count; e += NTHR) lds[RL_Y2.off + e] = 0.0_r;
+  pf.commitDynamics(lds + RL_STG.off + ((N - 1) & 1) * STG_B, OFF_TAIL, tid, jointRowMask<PFB, NTHR>(tid), dtLast);
+}
+
 #ifdef QM_RICCATI_TIMING
 #define QM_TK , qmTs + 19
 #else
@@ -286,9 +296,8 @@ __device__ __forceinline__ void riccatiGainsOut(const real* kst, real* gain, int
 template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIMD riccati_kernel(RiccatiArgs a) {
   static_assert(NW == 4, "tile ownership below is written for four wavefronts");
   QM_DYNAMIC_LDS(lds);
-  QM_POISON_LDS(lds, RICCATI_LDS_DOUBLES);
+  QM_POISON_LDS(lds, RICCATI_LDS_REALS);
   constexpr int NTHR = NW * 64;
-  constexpr int PFB = (OFF_TAIL / 2 + NTHR - 1) / NTHR;
   constexpr int NCP = 128;                                      // the same copy during the factorisation: by wavefronts 1 and 3 (wavefront 2 forms a tile AND the deferred gains: it is as long as the factorisation itself)
   constexpr int PFW = (OFF_TAIL / 2 + NCP - 1) / NCP;
   // forward sweep: only the head of the record (A~ B~ rows 0..11, Px Pu rows 12..29) and b~ q~ r~, Pu rows 0..11, Pe (its tail) are read; Q~ P~ R~ in between are not
@@ -301,42 +310,15 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
   const int inst = blockIdx.x;
   if (a.done[inst]) return;   // workgroup uniform
   const int N = a.N;
-  real* S = lds + R_S; real* Y = lds + R_Y; real* T = lds + R_T;
-  real* red = lds + R_SCR;
+  real* S = lds + RL_S.off; real* Y = lds + RL_Y.off; real* T = lds + RL_T.off;
+  real* red = lds + RL_ARMIJO.off;
   const real* stagesI = a.stages + size_t(inst) * (N + 1) * STAGE_DOUBLES;
   const real* gainsI = a.gains + size_t(inst) * N * GAIN_DOUBLES;
   const int* ncI = a.stageNc + size_t(inst) * (N + 1);
   const real* dtI = a.dtgrid + size_t(inst) * (N + 1);
   int status = 0;
 
-  // ---- terminal value function S_N = Q_N, s_N = q_N (zero padded), and the first stage to process
-  {
-    const real* rec = stagesI + size_t(N) * STAGE_DOUBLES;
-    // ONE memory round trip for the whole prologue: the record of stage N - 1 is requested first, the terminal Q_N with s_N = q_N as its row 30 (the B operands
-    // carry a unit entry at (30, 30)) behind it, and nothing is waited for before all of them are on their way (were three round trips and a barrier in a row: Q_N,
-    // then q_N into the row the first pass had zeroed, then the record)
-    StagePrefetch<PFB, NTHR> pf;
-    pf.issue(stagesI + size_t(N - 1) * STAGE_DOUBLES, OFF_TAIL, tid);
-    const real dtLast = dtI[N - 1];
-    {   // all of a thread's loads before its first LDS store (a load may not pass the store in front of it: seven memory round trips in a row otherwise)
-      constexpr int NS = (32 * LDS_S + NTHR - 1) / NTHR;
-      real sv[NS];
-#pragma unroll
-      for (int q = 0; q < NS; ++q) {
-        const int e = tid + q * NTHR, i = e / LDS_S, j = e % LDS_S;
-        const bool inQ = e < 32 * LDS_S && i < 30 && j < 30, inq = e < 32 * LDS_S && i == 30 && j < 30;
-        sv[q] = (inQ || inq) ? rec[inq ? OFF_qt + j : OFF_QT + i * 30 + j] : 0.0_r;
-      }
-#pragma unroll
-      for (int q = 0; q < NS; ++q) QM_KEEP(sv[q]);
-#pragma unroll
-      for (int q = 0; q < NS; ++q) { const int e = tid + q * NTHR; if (e < 32 * LDS_S) S[e] = sv[q]; }
-    }
-    for (int e = tid; e < 2 * W_DOUBLES + 2 * LT_DOUBLES + 2 * GAIN_DOUBLES; e += NTHR) lds[R_W + e] = 0.0_r;   // W, L, gains images of both parities (contiguous)
-    for (int e = tid; e < 2 * 32 * LDS_Y; e += NTHR) Y[e] = 0.0_r;        // Y, T (contiguous)
-    for (int e = tid; e < 16 * LDS_Y; e += NTHR) lds[R_Y2 + e] = 0.0_r;
-    pf.commitDynamics(lds + R_STG + ((N - 1) & 1) * STG_B, OFF_TAIL, tid, jointRowMask<PFB, NTHR>(tid), dtLast);
-  }
+  riccatiPrologue<NTHR>(lds, stagesI, dtI, N, tid);
   __syncthreads();
   QM_TICK_DECL;
 
@@ -402,8 +384,8 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
   const unsigned long long jmW = copier ? jointRowMask<PFW, NCP>(ptid) : 0ull;   // which of my units of the staged copy are joint-row entries
 #pragma unroll 1
   for (int k = N - 1; k >= 0; --k) {
-    const real* stg = lds + R_STG + (k & 1) * STG_B;        // this stage (committed during the previous one)
-    real* stgNext = lds + R_STG + ((k + 1) & 1) * STG_B;    // buffer of stage k - 1
+    const real* stg = lds + RL_STG.off + (k & 1) * STG_B;        // this stage (committed during the previous one)
+    real* stgNext = lds + RL_STG.off + ((k + 1) & 1) * STG_B;    // buffer of stage k - 1
     const int nt = 30 - ncCur;
     // constraint rows of the stage after this one: wanted at the END of this stage.  Requested here through an address the compiler cannot prove uniform, and made
     // a scalar down there: as a uniform load it was a global_load followed at once by s_waitcnt vmcnt(0) + v_readfirstlane -- a trip to the L2 (~300 cycles) on
@@ -415,7 +397,7 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
     // ---- P1 + P2: wavefront w owns the 16 columns [16 w, 16 w + 16) of Y and of T
     const bool splitK = nTiles == 3;                 // (wave uniform, per stage)
     const real y2On = splitK ? 1.0_r : 0.0_r;        // consumers of Y rows 16..31 add Y2 times this (Y2 always holds finite numbers)
-    real* Y2 = lds + R_Y2;
+    real* Y2 = lds + RL_Y2.off;
     // P6a of one 16 x 16 tile (tm, tn) of [Q~ | q~] + A~^T [S A~ | y] (needs all of Y: behind the stage's first barrier), in accumulator layout
     auto p6aTile = [&](int tm, int tn) -> QmAcc {
       const int j = tn * 16 + l16;
@@ -434,7 +416,7 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
         av[ks] = stg[OFF_AT + kc * 30 + ai]; bw[ks] = Y[kk * LDS_Y + j];   // A~^T[i][k] = A~[k][i]
       }
 #pragma unroll
-      for (int ks = 4; ks < 8; ++ks) bw[ks] = fma(y2On, lds[R_Y2 + (4 * (ks - 4) + h) * LDS_Y + j], bw[ks]);   // rows 16..31 of Y: the other half of the k sum (P1)
+      for (int ks = 4; ks < 8; ++ks) bw[ks] = fma(y2On, lds[RL_Y2.off + (4 * (ks - 4) + h) * LDS_Y + j], bw[ks]);   // rows 16..31 of Y: the other half of the k sum (P1)
       QmAcc c;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -449,7 +431,7 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
     };
     // The off-diagonal tile (0,1) belongs to wavefront 2, which also forms the gains of the previous stage -- with both it was the longest wavefront of the
     // factorisation phase once the factorisation had lost its tail (round 6).  In stages with three column tiles (m~ <= 16) wavefront 3 has no part in P2:
-    // it forms that tile THERE and parks it in the free square of the symmetrisation scratch (rows 0..15, columns 16..31); wavefront 2 picks it up behind its gains.
+    // it forms that tile THERE and parks it in the free square of the symmetrisation scratch (riccati_lds.h: SYM_PARK); wavefront 2 picks it up behind its gains.
     const bool early01 = nTiles == 3;
     if (wave < nTiles) {
       QmAcc c0, c1;
@@ -547,14 +529,14 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
     if (wave == 3 && early01) {
       const QmAcc ce = p6aTile(0, 1);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) lds[R_SYM + (h + 4 * r) * LDS_TS + 16 + l16] = ce[r];
+      for (int r = 0; r < 4; ++r) lds[RL_SYM.off + (h + 4 * r) * LDS_TS + SYM_PARK + l16] = ce[r];
     }
     QM_TICK(3);
     QM_LDS_BARRIER();
     QM_TICK(4);
     // ---- P3 on wavefront 0; P6a + deferred gains on wavefronts 1..3
-    real* W = lds + R_W + (k & 1) * W_DOUBLES;
-    real* LL = lds + R_LT + (k & 1) * LT_DOUBLES;
+    real* W = lds + RL_W.off + (k & 1) * W_REALS;
+    real* LL = lds + RL_LT.off + (k & 1) * LT_REALS;
     // S' is symmetric: only the tiles (0,0), (0,1) and (1,1) of the 32 x 32 update are formed, by wavefronts 1, 2, 3; the tile (1,0) is
     // the mirror of (0,1).  Tile t = (t >> 1, t & 1).
     const int myTile = wave == 1 ? 0 : (wave == 2 ? 1 : 3);
@@ -582,7 +564,7 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
       const int tm = myTile >> 1, tn = myTile & 1, j = tn * 16 + l16;
       if (wave != 2 || !early01) c6 = p6aTile(tm, tn);
       if (wave != 2) {    // diagonal tiles (0,0) and (1,1); column 30 (s') and the rows / columns beyond 29 stay as they are
-        real* SYM = lds + R_SYM;
+        real* SYM = lds + RL_SYM.off;
 #pragma unroll
         for (int r = 0; r < 4; ++r) SYM[(tm * 16 + h + 4 * r) * LDS_TS + j] = c6[r];
         QM_WAVE_SYNC();   // the transposed read meets this wavefront's own writes (LDS operations of one wavefront complete in order)
@@ -598,13 +580,13 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
       //      stage ago (stage k + 2) to HBM
       if (wave == 2) {
         if (k + 1 < N && lane < 31)
-          riccatiGains(lds + R_W + ((k + 1) & 1) * W_DOUBLES, lds + R_LT + ((k + 1) & 1) * LT_DOUBLES, 30 - ncPrev, lane, lds + R_KST + ((k + 1) & 1) * GAIN_DOUBLES);
+          riccatiGains(lds + RL_W.off + ((k + 1) & 1) * W_REALS, lds + RL_LT.off + ((k + 1) & 1) * LT_REALS, 30 - ncPrev, lane, lds + RL_KST.off + ((k + 1) & 1) * GAIN_DOUBLES);
         if (early01) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) c6[r] = lds[R_SYM + (h + 4 * r) * LDS_TS + 16 + l16];
+          for (int r = 0; r < 4; ++r) c6[r] = lds[RL_SYM.off + (h + 4 * r) * LDS_TS + SYM_PARK + l16];
         }
       } else if (k + 2 < N) {
-        riccatiGainsOut(lds + R_KST + (k & 1) * GAIN_DOUBLES, a.gains + (size_t(inst) * N + k + 2) * GAIN_DOUBLES, wave == 1 ? lane : 64 + lane);
+        riccatiGainsOut(lds + RL_KST.off + (k & 1) * GAIN_DOUBLES, a.gains + (size_t(inst) * N + k + 2) * GAIN_DOUBLES, wave == 1 ? lane : 64 + lane);
       }
       if (copier) pf.commitDynamics(stgNext, OFF_TAIL, ptid, jmW, stg[OFF_DTPREV]);   // stage k - 1 lands in the other buffer, its joint rows as A~ / B~ (its step came with stage k)
     }
@@ -623,15 +605,15 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
 #pragma unroll
       for (int ks = 0; ks < 5; ++ks) qmMfma(c6, av[ks], bw[ks]);
       // one store per accumulator register, no branch: an entry of the padding (row / column 30, 31: they must stay zero) goes to a scratch word of the
-      // symmetrisation square (free here), the s' entry (column 30) to row 30 of S; the mirror image of the off-diagonal tile likewise
-      real* sink = lds + R_SYM + lane;
+      // symmetrisation scratch (free here: riccati_lds.h, SYM_SINK), the s' entry (column 30) to row 30 of S; the mirror image of the off-diagonal tile likewise
+      real* sink = lds + RL_SYM.off + SYM_SINK + lane;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = tm * 16 + h + 4 * r;
         const bool inS = i < 30 && j < 30;
         real* dst = inS ? S + i * LDS_S + j : ((i < 30 && j == 30) ? S + 30 * LDS_S + i : sink);
         *dst = c6[r];
-        if (wave == 2) { real* mir = inS ? S + j * LDS_S + i : sink + 64; *mir = c6[r]; }
+        if (wave == 2) { real* mir = inS ? S + j * LDS_S + i : sink + (SYM_SINK_MIRROR - SYM_SINK); *mir = c6[r]; }
       }
     }
     QM_TICK(8);
@@ -642,10 +624,10 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
     ncPrev = ncCur; ncCur = qmReadLaneInt(qmOpaqueLane(ncLoadV), 0);
   }
   // ---- gains of stage 0 (nobody factorises any more)
-  if (wave == 2) { if (lane < 31) riccatiGains(lds + R_W, lds + R_LT, 30 - ncPrev, lane, lds + R_KST); }
-  else if (wave != 0 && N > 1) riccatiGainsOut(lds + R_KST + GAIN_DOUBLES, a.gains + (size_t(inst) * N + 1) * GAIN_DOUBLES, wave == 1 ? lane : 64 + lane);
+  if (wave == 2) { if (lane < 31) riccatiGains(lds + RL_W.off, lds + RL_LT.off, 30 - ncPrev, lane, lds + RL_KST.off); }
+  else if (wave != 0 && N > 1) riccatiGainsOut(lds + RL_KST.off + GAIN_DOUBLES, a.gains + (size_t(inst) * N + 1) * GAIN_DOUBLES, wave == 1 ? lane : 64 + lane);
   QM_LDS_BARRIER();
-  if (wave == 1 || wave == 3) riccatiGainsOut(lds + R_KST, a.gains + size_t(inst) * N * GAIN_DOUBLES, wave == 1 ? lane : 64 + lane);
+  if (wave == 1 || wave == 3) riccatiGainsOut(lds + RL_KST.off, a.gains + size_t(inst) * N * GAIN_DOUBLES, wave == 1 ? lane : 64 + lane);
 
   // ================================================================== forward substitution
   // The recursion  du~ = K dx + k,  dx+ = A~ dx + B~ du~ + b~  runs on wavefront 0 alone (a v_mfma_f64 holds a SIMD's matrix pipe for 64
@@ -663,7 +645,7 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
   constexpr int PFH3 = (FWD_HEAD / 2 + NPF - 1) / NPF, PFT3 = (FWD_SMALL / 2 + NPF - 1) / NPF, PFG3 = (GAIN_DOUBLES / 2 + NPF - 1) / NPF;
   constexpr int PFS = (FWD_SMALL / 2 + NTHR - 1) / NTHR;
   QM_TICK(12);
-  __syncthreads();   // full barrier: the gains written to HBM above are read back below
+  __syncthreads();   // full barrier: the gains written to HBM above are read back below; the forward overlays (riccati_lds.h: RO_RING, RO_ZV) are first written behind it
   {
     StagePrefetch<PFH, NTHR> ph;
     StagePrefetch<PFS, NTHR> pt;
@@ -671,13 +653,13 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
     ph.issue(stagesI, FWD_HEAD, tid);
     pt.issue(stagesI + FWD_TAIL0, FWD_SMALL, tid);
     pg.issue(gainsI, GAIN_DOUBLES, tid);
-    for (int e = tid; e < 3 * ZV; e += NTHR) lds[F_ZV + e] = 0.0_r;
-    ph.commit(lds + R_STG, FWD_HEAD, tid);   // the forward sweep works on the record as it is: rows 12..29 of the head are Px / Pu (see the chain below)
-    pt.commit(lds + R_STG + FWD_TAIL0, FWD_SMALL, tid);
-    pg.commit(lds + R_STG + STAGE_DOUBLES, GAIN_DOUBLES, tid);
+    for (int e = tid; e < 3 * ZV; e += NTHR) lds[RO_ZV.off + e] = 0.0_r;
+    ph.commit(lds + RO_RING.off, FWD_HEAD, tid);   // the forward sweep works on the record as it is: rows 12..29 of the head are Px / Pu (see the chain below)
+    pt.commit(lds + RO_RING.off + FWD_TAIL0, FWD_SMALL, tid);
+    pg.commit(lds + RO_RING.off + STAGE_DOUBLES, GAIN_DOUBLES, tid);
   }
   __syncthreads();
-  if (tid < 30) lds[F_ZV + tid] = a.x0[size_t(inst) * 30 + tid] - a.X[size_t(inst) * (N + 1) * 30 + tid];
+  if (tid < 30) lds[RO_ZV.off + tid] = a.x0[size_t(inst) * 30 + tid] - a.X[size_t(inst) * (N + 1) * 30 + tid];
   real armijo = 0.0_r;
   __syncthreads();
   const bool upper = lane >= 32;            // second half of the wavefront: the second half of every dot product
@@ -705,8 +687,8 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
     QM_TICK(14);
     if (wave == 0) {
       if (k < N) {
-        const real* stg = lds + R_STG + sl * STG_F; const real* gn = stg + STAGE_DOUBLES;
-        real* zv = lds + F_ZV + sl * ZV; real* zvNext = lds + F_ZV + slNext * ZV;
+        const real* stg = lds + RO_RING.off + sl * STG_F; const real* gn = stg + STAGE_DOUBLES;
+        real* zv = lds + RO_ZV.off + sl * ZV; real* zvNext = lds + RO_ZV.off + slNext * ZV;
         // Every product is split in the middle between the two halves of the wavefront (row r of the product on lanes r and 32 + r): the same instruction
         // stream on both halves, so all LDS operands are requested before the first multiply-add, and the part of dx+ that has to wait for du~ is 9
         // multiply-adds, not 18.  The head of the record is used as it is (layout.h): rows 0..11 are [A~ | B~], rows 12..29 [Px | Pu], so with
@@ -760,7 +742,7 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
       const bool landing = wave >= 2 && ((k ^ wave) & 1) == 0;   // wavefront 2 in the even iterations, wavefront 3 in the odd ones
       if (landing) {
         if (k + 1 < N) {
-          real* dst = lds + R_STG + slNext * STG_F;
+          real* dst = lds + RO_RING.off + slNext * STG_F;
           ph.commit(dst, FWD_HEAD, lane);
           pt.commit(dst + FWD_TAIL0, FWD_SMALL, lane);
           pg.commit(dst + STAGE_DOUBLES, GAIN_DOUBLES, lane);
@@ -770,8 +752,8 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
       QM_TICK(16);
       if (k > 0) {
         const int j = k - 1;
-        const real* stg = lds + R_STG + slPrev * STG_F;
-        const real* zv = lds + F_ZV + slPrev * ZV;
+        const real* stg = lds + RO_RING.off + slPrev * STG_F;
+        const real* zv = lds + RO_ZV.off + slPrev * ZV;
         if (wave == 1) {   // du = Pe + Px dx + Pu du~: joint rows from the chain's s, force rows from the contact mode (layout.h: puColumnOfForce)
           if (lane < 30) {
             const int puCol = puColumnOfForce(int(stg[OFF_MODE]), lane < 12 ? lane : 0);
@@ -796,7 +778,7 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
   QM_TICK(13);
   QM_TICK_FLUSH((threadIdx.x >> 6) * 32, blockIdx.x == 0 && (threadIdx.x & 63) == 0);
   if (wave == 2 && lane < 30) {   // terminal node: dx_N sits in slot N % 3
-    const real dxl = lds[F_ZV + (N % 3) * ZV + lane];
+    const real dxl = lds[RO_ZV.off + (N % 3) * ZV + lane];
     a.dX[(size_t(inst) * (N + 1) + N) * 30 + lane] = dxl;
     armijo += stagesI[size_t(N) * STAGE_DOUBLES + OFF_qt + lane] * dxl;
   }

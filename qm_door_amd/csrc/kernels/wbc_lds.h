@@ -4,6 +4,7 @@
 #pragma once
 #include "../../../include/qmgpu.h"
 #include "gpu_rt.h"
+#include "lds_region.h"
 
 namespace qmk {
 
@@ -13,13 +14,7 @@ constexpr int QP_KMAX = 28;                              // pinned rows the smal
 constexpr int QP_SLD = QP_KMAX + 1;
 constexpr int WBC_BODY_STRIDE = 33;                      // per body: R9 p3 c3 I6 w3 al3 vo3 ao3
 
-// `count` elements of T, `off` doubles behind the LDS base; a region starts where the one before it ends.
-template <class T> struct LdsRegion {
-  int off, count;
-  constexpr int doubles() const { return int((count * sizeof(T) + sizeof(double) - 1) / sizeof(double)); }
-  constexpr int end() const { return off + doubles(); }
-};
-template <class T, class U> constexpr LdsRegion<T> ldsAfter(LdsRegion<U> prev, int count) { return LdsRegion<T>{prev.end(), count}; }
+// (LdsRegion, ldsAfter: lds_region.h; this kernel's regions count in doubles)
 // An int region of LDS that is declared in doubles: the one place where the element type changes (a reinterpret_cast in effect, spelt through void*).  No int region shares storage with a double region.
 __device__ __forceinline__ int* ldsInts(double* base, LdsRegion<int> r) { return static_cast<int*>(static_cast<void*>(base)) + 2 * r.off; }
 

@@ -168,7 +168,6 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
 #ifdef QM_RICCATI_TIMING
   const unsigned long long qmWgStart = wall_clock64();
 #endif
-  int nc = 0;
   QM_TICK(0);
 #pragma unroll 1
   for (int stage = 0; stage < 2; ++stage) {
@@ -240,17 +239,16 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
           auto putVel = [&](int row, Du3 hv, int axisIdx, real gainZ) {
             putGlobal(AD_CD, row, hv.d, hv.e, isVal ? hv.v : (dd == axisIdx ? 1.0_r : (dd == 5 ? gainZ : 0.0_r)));
           };
+          const int row = firstRowOfFoot(mode, c);   // (contact_rows.h: the rows of a foot, and which of them are stored)
           if (contact) {  // zeroVelocity (QMInterface.cpp:126, 324-339; Ax(2,2) = positionErrorGain)
-            putVel(nc, vf.x, 0, 0.0_r); putVel(nc + 1, vf.y, 1, 0.0_r);
-            putVel(nc + 2, vf.z + st.position_error_gain * (x[8] + r.z), 2, st.position_error_gain);
-            nc += 3;
+            putVel(row, vf.x, 0, 0.0_r); putVel(row + 1, vf.y, 1, 0.0_r);
+            putVel(row + 2, vf.z + st.position_error_gain * (x[8] + r.z), 2, st.position_error_gain);
           } else {  // zeroForce (QMInterface.cpp:123-124) then normalVelocity (QMPreComputation.cpp:56-66)
-            // rows nc .. nc + 2: C = 0, D = unit vector on force input 3 c + q, e = u[3 c + q] -- known from the mode alone, so they are NOT stored:
+            // the zero-force rows: C = 0, D = unit vector on force input 3 c + q, e = u[3 c + q] -- known from the mode alone, so they are NOT stored:
             // lq_node_kernel synthesises them (1.5 KB per swing foot and node each way)
             real zp, zv;
             swingReference(st, sched, c, t, phase, zp, zv);
-            putVel(nc + 3, vf.z - zv + st.position_error_gain * (x[8] + r.z - zp), 2, st.position_error_gain);
-            nc += 4;
+            putVel(row + ZERO_FORCE_ROWS, vf.z - zv + st.position_error_gain * (x[8] + r.z - zp), 2, st.position_error_gain);
           }
         }
       }
@@ -363,7 +361,7 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
       }
     }
   }
-  if (live && dd == 0) { a.stageNc[gnode] = nc; a.nodeMode[gnode] = mode; }
+  if (live && dd == 0) { a.stageNc[gnode] = terminal ? 0 : constraintCount(mode); a.nodeMode[gnode] = mode; }
   QM_TICK(6);
   QM_TICK_FLUSH(320, blockIdx.x == 1000 && lane == 0);
 #ifdef QM_RICCATI_TIMING

@@ -86,10 +86,8 @@ __global__ void mpc_init_kernel(InitArgs a) {
     if (k < a.N && !a.warmU) {   // QMInitializer: the weight shared by the feet in contact at the node's time, nothing else -- stores only, nothing to wait for
       real* u = a.U + (size_t(inst) * a.N + k) * 30;
       const int mode = modes[phase];
-      int n = 0;
-      for (int c = 0; c < 4; ++c) n += contactOf(mode, c) ? 1 : 0;
-      const real w = n > 0 ? a.P->model.total_mass * st.gravity / n : 0.0_r;
-      for (int i = 0; i < 30; ++i) u[i] = (i < 12 && i % 3 == 2 && contactOf(mode, i / 3)) ? w : 0.0_r;
+      const real w = nominalNormalForce(a.P->model.total_mass, st.gravity, mode);
+      for (int i = 0; i < 30; ++i) u[i] = nominalInputEntry(mode, i, w);
     }
   }
   // The copied trajectories (x0 / warm states, warm inputs) as flat copies, consecutive threads consecutive entries, eight entries per thread and pass with all

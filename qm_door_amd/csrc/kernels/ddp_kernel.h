@@ -15,6 +15,7 @@
 // a wavefront carry different (instance, step length) pairs rather than nodes.
 #pragma once
 #include "layout.h"
+#include "contact_rows.h"
 #include "linesearch_kernel.h"
 
 namespace qmk {
@@ -94,7 +95,7 @@ __global__ void __launch_bounds__(64) ddp_rollout_kernel(DdpArgs a) {
         real s = alpha * rec[OFF_PE + i];
         if (i >= 12) for (int c = 0; c < 30; ++c) s += rec[offPxRow(i) + c] * dx[c];   // rows 0..11 (force inputs) of Px are structurally zero and not stored (layout.h)
         if (i >= 12) { for (int r = 0; r < nt; ++r) s += rec[offPuRow(i) + r] * dut[r]; }
-        else { const int pc = puColumnOfForce(int(rec[OFF_MODE]), i); if (pc >= 0) s += dut[pc]; }   // force rows of Pu: unit vectors, not stored (layout.h)
+        else { const int pc = puColumnOfForce(int(rec[OFF_MODE]), i); if (pc >= 0) s += dut[pc]; }   // force rows of Pu: unit vectors, not stored (layout.h, contact_rows.h)
         u[i] = un[i] + s;
       }
     }

@@ -135,9 +135,7 @@ template <class WP> __device__ __attribute__((noinline)) void nodePerformance(co
   // tracking cost
   int tIdx; real tAlpha;
   timeSegment(tTimes, K, t, tIdx, tAlpha);
-  int nStance = 0;
-  for (int k = 0; k < 4; ++k) nStance += contactOf(mode, k) ? 1 : 0;
-  const real fzNom = nStance > 0 ? md.total_mass * st.gravity / nStance : 0.0_r;
+  const real fzNom = nominalNormalForce(md.total_mass, st.gravity, mode);
   // deviations once, in registers; then the two quadratic forms fully unrolled: the weights are read with compile-time offsets from
   // wave-uniform addresses (scalar loads), x / u / the reference are not touched again.  (The rolled double loop re-read x[j], u[j] and the
   // reference states from HBM for each of the 900 (i, j) pairs: most of the kernel's time.)  Same order of operations as before.
@@ -145,7 +143,7 @@ template <class WP> __device__ __attribute__((noinline)) void nodePerformance(co
 #pragma unroll
   for (int j = 0; j < 30; ++j) {
     dx[j] = x[j] - xReference(tStates, K, tIdx, tAlpha, j);
-    du[j] = u[j] - ((j < 12 && (j % 3) == 2 && contactOf(mode, j / 3)) ? fzNom : 0.0_r);
+    du[j] = u[j] - nominalInputEntry(mode, j, fzNom);
   }
   if (weightStructure == 1) {   // wave uniform
 #pragma unroll

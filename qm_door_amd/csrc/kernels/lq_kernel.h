@@ -11,44 +11,12 @@
 // read from LDS (or assembled in registers) in the lane layout of gpu_rt.h; results leave in accumulator layout.
 #pragma once
 #include "ad_kernel.h"
+#include "contact_rows.h"
+#include "lq_lds.h"
 
 namespace qmk {
 
-// LDS of lq_node_kernel (doubles): 12.7 KiB per node, twelve nodes per CU = THREE wavefronts per SIMD.  The kernel is latency bound
-// (readlane chains, LDS round trips, dependent matrix-core accumulations): at one wavefront per SIMD it ran 1.10 ms per launch, at
-// two 0.44 ms, at three 0.39 ms.  What keeps it this small:
-//   * Pall = [Px | Pe | 0 | Pu] is stored for its 18 dense joint-velocity rows only; the 12 force rows are unit vectors / pinned
-//     values and are synthesised into the matrix-core operands from registers;
-//   * R' and Q never enter LDS: the operand / accumulator entries are assembled where they are needed from the constant
-//     matrices (global, L1 resident) plus the few barrier terms parked in LDS;
-//   * the dense rows of [A | B] never enter LDS: products (1) reads its operands straight from the AD rows (global, cache resident);
-//   * W = R Pall is produced one 16-column tile at a time and never enters LDS: in the fp64 accumulator map register r of a lane
-//     holds row h + 4 r, which is the row of k step r it supplies as a B operand (gpu_rt.h; the fp32 build permutes A rows to the
-//     same map), so the tile feeds G = Pall^T W from the registers it was accumulated in;
-//   * the zero rows of Q_v (18..31) and of Y (12..15) are synthesised into the operands, not stored.
-// Regions and live ranges (QM_TICK sections; every hand-off between aliases crosses a QM_WAVE_SYNC()):
-//   X   x u x_next dx [4][32]      ticks 0..3  (dead at the sync in front of the QR, tick 5)
-//       Q_v [18][LDQ]              tick 5 (published after the QR) .. the sync after Pall is complete (tick 6)
-//       fin[64], red[64]           at X + 128, X + 192: red in the terminal path (tick 1) and after products (1); fin in products
-//                                  (2)(3) -- neither meets Q_v, and neither overlaps x u x_next dx
-//   PA  [C | D_v] [16][CDW]        ticks 0..5 (dead at the sync in front of the QR)
-//       Y [12][LDY]                tick 5: published after the QR, read by -Q_v1 Y (dead at the sync in front of the Pall stores)
-//       Pall rows 12..29 [18][PAW] tick 5 .. the end of products (2)(3)
-//   EEJ [6][32]                    ticks 0..9
-//   VEC b r e eeh pe fb ddp ddv q cost  ticks 0..9
-constexpr int PAW = 50;                      // row stride of the dense rows of Pall (columns 0..29 Px, 30 Pe, 31 zero, 32..32+m~-1 Pu)
-constexpr int CDW = 49;                      // row stride of [C | D_v] (48 used: the 30 state columns and the 18 joint-velocity columns)
-constexpr int LDQ = 18, LDY = 34;
-constexpr int X_DOUBLES = 18 * LDQ;
-constexpr int L_X = 0;                       // X: x u x_next dx [4][32] (+ fin[64] red[64]) | Q_v [18][LDQ]
-constexpr int L_XU = L_X, L_QS = L_X, L_FIN = L_X + 128, L_RED = L_X + 192;
-constexpr int L_PA = L_X + X_DOUBLES;        // rows 12..29 of Pall [18][PAW]  /  [C | D_v] [16][CDW]  /  Y [12][LDY]
-constexpr int L_YM = L_PA;
-constexpr int L_EEJ = L_PA + 18 * PAW;       // EE error Jacobian [6][32]
-constexpr int L_VEC = L_EEJ + 192;           // b[30] r[30] e[16] eeh[6] (+2) | pe[12] fb[36] ddp[6] ddv[6] (+4) | q[30] (+2) | cost[30] (+2)
-constexpr int LQ_LDS_DOUBLES = L_VEC + 84 + 64 + 32 + 32;
-static_assert(16 * CDW <= 18 * PAW && 12 * LDY <= 18 * PAW && L_RED + 64 <= X_DOUBLES, "aliases must fit");
-static_assert(LQ_LDS_DOUBLES * sizeof(real) * 12 <= 160 * 1024, "twelve nodes per CU");
+// (the LDS of lq_node_kernel -- regions, overlays, live ranges, strides: lq_lds.h; the row structure of a contact mode: contact_rows.h)
 
 // Both kernels of this file run one wavefront per workgroup: LDS hand-offs between lanes need no hardware barrier (a wavefront's
 // LDS operations complete in issue order), only the compiler fence QM_WAVE_SYNC() -- and, unlike __syncthreads(), that does not
@@ -80,10 +48,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
   const SettingsR& st = a.P->settings;
   const real* bcs = a.Rw + QM_RW_DERIVED;   // barrier constants (layout.h)
 
-  real* PA = lds + L_PA; real* CD = lds + L_PA;
-  real* EEJ = lds + L_EEJ; real* bv = lds + L_VEC; real* rv = bv + 30; real* ev = rv + 30; real* eeh = ev + 16;
-  real* pev = bv + 84; real* fb = pev + 12; real* ddp = fb + 36; real* ddv = ddp + 6; real* qv = bv + 148; real* cst = qv + 32;
-  real* fin = lds + L_FIN; real* red = lds + L_RED;
+  real* PA = lds + LO_PALL.off; real* CD = lds + LO_CD.off; real* EEJ = lds + LQ_EEJ.off;
+  real* bv = lds + LV_B.off; real* rv = lds + LV_R.off; real* ev = lds + LV_E.off; real* eeh = lds + LV_EEH.off; real* pev = lds + LV_PE.off;
+  real* fb = lds + LV_FB.off; real* ddp = lds + LV_DDP.off; real* ddv = lds + LV_DDV.off; real* qv = lds + LV_Q.off; real* cst = lds + LV_COST.off;
+  real* fin = lds + LO_FIN.off; real* red = lds + LO_RED.off;
 
   QM_TICK_DECL;
   const real* tg = a.tgrid + size_t(inst) * (a.N + 1);
@@ -93,7 +61,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
   const real* uG = terminal ? a.zeros : a.U + (size_t(inst) * a.N + node) * 30;
   // x, u, x_next and the reference state are read many times with wave-uniform indices: one vector load each into LDS instead of
   // chains of dependent scalar loads.  They live in region X and are dead before the QR publishes Q_v there.
-  real* x = lds + L_XU; real* u = x + 32; real* xnext = x + 64; real* dx = x + 96;   // dx = x - x_ref
+  real* x = lds + LO_XU.off; real* u = x + XU_LD; real* xnext = x + 2 * XU_LD; real* dx = x + 3 * XU_LD;   // dx = x - x_ref
   const Schedule sched{a.schedNum[inst], a.schedTimes + size_t(inst) * QMGPU_MAX_EVENTS, a.schedModes + size_t(inst) * (QMGPU_MAX_EVENTS + 1)};
   const int phase = a.nodePhase[size_t(inst) * (a.N + 1) + node];
   const int mode = sched.modes[phase];
@@ -108,34 +76,21 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
   QM_TICK(0);
   // ---- rows of the AD sweep (ad_node_kernel)
   const real* ad = a.adrows + (size_t(inst) * (a.N + 1) + node) * AD_DOUBLES;
-  int nc = 0;
+  // what the contact mode says about the rows (contact_rows.h), wave uniform and indexed with compile-time constants only, so that the arrays stay in registers
+  const int nc = terminal ? 0 : constraintCount(mode);
+  const int firstStored = firstStoredRow(mode);   // a row ad_node_kernel stored
+  const int nv = velocityRowCount(mode), nStF = freeForceCount(mode);   // velocity rows; free (stance) force inputs
+  constexpr int NVMAX = 12;
   int zfForce[NCMAX];   // force input a zero-force row pins (swing foot), or -1: those rows are not stored by ad_node_kernel (C = 0, D = unit vector, e = u)
+  int vrOf[NVMAX];      // CD row of velocity row r
+  int frcRowOf[12];     // CD row pinning force input i (swing foot), or -1 (stance foot: free)
+  int puColOf[12];      // Pu column of a free force input, or -1
 #pragma unroll
-  for (int r = 0; r < NCMAX; ++r) zfForce[r] = -1;
-  if (!terminal) {
+  for (int r = 0; r < NCMAX; ++r) zfForce[r] = terminal ? -1 : zeroForceInputOfRow(mode, r);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (contactOf(mode, k)) nc += 3;
-      else {
+  for (int r = 0; r < NVMAX; ++r) vrOf[r] = rowOfVelocityRow(mode, r);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
-#pragma unroll
-          for (int r = 0; r < NCMAX; ++r) if (r == nc + q) zfForce[r] = 3 * k + q;
-        }
-        nc += 4;
-      }
-    }
-  }
-  const int firstStored = contactOf(mode, 0) ? 0 : 3;   // first row ad_node_kernel stored: a stance foot's first velocity row or a swing foot's normal-velocity row
-  // force input pinned by row r of the constraint set, or -1 (recomputed from the mode: the debug dump below indexes it with a run-time row)
-  auto zeroForceInputOf = [&](int r) {
-    int row = 0, res = -1;
-    for (int k = 0; k < 4; ++k) {
-      if (contactOf(mode, k)) row += 3;
-      else { if (r >= row && r < row + 3) res = 3 * k + (r - row); row += 4; }
-    }
-    return res;
-  };
+  for (int i = 0; i < 12; ++i) { frcRowOf[i] = pinningRowOfForce(mode, i); puColOf[i] = puColumnOfForce(mode, i); }
   {
     real cdv[NCMAX], eev[6];   // all global loads in flight before the first LDS store
 #pragma unroll
@@ -152,7 +107,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
       if (r < nc) { if (lane < 30) CD[r * CDW + lane] = cdv[r]; else if (lane >= 42 && lane < 60) CD[r * CDW + lane - 12] = cdv[r]; else if (lane == 60) ev[r] = cdv[r]; }
     }
 #pragma unroll
-    for (int q = 0; q < 6; ++q) { if (lane < 32) EEJ[q * 32 + lane] = eev[q]; else if (lane == 60) eeh[q] = eev[q]; }
+    for (int q = 0; q < 6; ++q) { if (lane < EEJ_LD) EEJ[q * EEJ_LD + lane] = eev[q]; else if (lane == 60) eeh[q] = eev[q]; }
   }
   real hf[3];   // f_e - f_ref (column 61 of the position rows, ad_node_kernel)
 #pragma unroll
@@ -184,7 +139,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
     real dd = 0.0_r;
     if (c < 30) {
 #pragma unroll
-      for (int q = 0; q < 6; ++q) qc += ((q < 3 ? muP : muO) * eeh[q] - (q < 3 ? muF * Ke * hf[q < 3 ? q : 0] : 0.0_r)) * EEJ[q * 32 + c];
+      for (int q = 0; q < 6; ++q) qc += ((q < 3 ? muP : muO) * eeh[q] - (q < 3 ? muF * Ke * hf[q < 3 ? q : 0] : 0.0_r)) * EEJ[q * EEJ_LD + c];
       if (c < 6) costPart += 0.5_r * (c < 3 ? muP : muO) * eeh[c] * eeh[c];
       if (c < 3) costPart += 0.5_r * muF * hf[c] * hf[c];
     }
@@ -227,7 +182,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
     const int ic = i < 30 ? i : 0, jc = j < 30 ? j : 0;
     real v = terminal ? 0.0_r : st.Q[ic * 30 + jc];
 #pragma unroll
-    for (int q = 0; q < 6; ++q) v += (q < 3 ? muP + muF * Ke * Ke : muO) * EEJ[q * 32 + ic] * EEJ[q * 32 + jc];
+    for (int q = 0; q < 6; ++q) v += (q < 3 ? muP + muF * Ke * Ke : muO) * EEJ[q * EEJ_LD + ic] * EEJ[q * EEJ_LD + jc];
     const real dg = ddp[ic >= 24 ? ic - 24 : 0];
     if (ic == jc && ic >= 24) v += dg;
     return (i < 30 && j < 30) ? v : 0.0_r;
@@ -256,20 +211,17 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
   // ---- input cost: R' + friction-cone and arm-velocity barriers.  Lane c < 30 forms the gradient entry c and the barrier terms
   //      of its column; the terms go to LDS (fb: four 3x3 friction blocks, ddv: arm-velocity diagonal), R' itself stays in HBM / L1.
   {
-    int nStance = 0;
-    for (int k = 0; k < 4; ++k) nStance += contactOf(mode, k) ? 1 : 0;
-    const real fzNom = nStance > 0 ? md.total_mass * st.gravity / nStance : 0.0_r;
+    const real fzNom = nominalNormalForce(md.total_mass, st.gravity, mode);
     if (c < 30) {
       real Rdu0 = 0.0_r, Rdu1 = 0.0_r;
 #pragma unroll
       for (int i = 0; i < 30; i += 2) {
-        const real un0 = (i < 12 && (i % 3) == 2 && contactOf(mode, i / 3)) ? fzNom : 0.0_r;
-        const real un1 = (i + 1 < 12 && ((i + 1) % 3) == 2 && contactOf(mode, (i + 1) / 3)) ? fzNom : 0.0_r;
+        const real un0 = nominalInputEntry(mode, i, fzNom), un1 = nominalInputEntry(mode, i + 1, fzNom);
         Rdu0 += a.Rw[i * 30 + c] * (u[i] - un0);
         Rdu1 += a.Rw[(i + 1) * 30 + c] * (u[i + 1] - un1);
       }
       const real Rdu = Rdu0 + Rdu1;
-      const real unomc = (c < 12 && (c % 3) == 2 && contactOf(mode, c / 3)) ? fzNom : 0.0_r;
+      const real unomc = nominalInputEntry(mode, c, fzNom);
       real rc = Rdu;
       costPart += 0.5_r * (u[c] - unomc) * Rdu;
       if (c >= 24) {  // arm joint velocity soft box (QMInterface.cpp:221-254)
@@ -327,7 +279,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
     for (int i = 0; i < 30; ++i) dbg[DBG_R + i * 30 + c] = rEntry(i, c);
     dbg[DBG_b + c] = bv[c]; dbg[DBG_r + c] = rv[c];
     for (int r = 0; r < nc; ++r) {
-      const int zf = zeroForceInputOf(r);
+      const int zf = zeroForceInputOfRow(mode, r);
       dbg[DBG_C + r * 30 + c] = zf >= 0 ? 0.0_r : ad[AD_CD + r * 64 + c];
       dbg[DBG_D + r * 30 + c] = zf >= 0 ? (c == zf ? 1.0_r : 0.0_r) : ad[AD_CD + r * 64 + 30 + c];
     }
@@ -351,34 +303,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
   // identity lanes end up with Q_v^T.  The reflector of step k is built by EVERY lane from column k, fetched with v_readlane from
   // lane k: no LDS hand-off, no divergent branch, no barrier inside the factorisation.
   const int nt = 30 - nc;  // projected input dimension m~
-  constexpr int NVMAX = 12;
-  int nv = 0, nStF = 0;     // velocity rows; free (stance) force inputs
-  int vrOf[NVMAX];          // CD row of velocity row r (wave uniform)
-  int frcRowOf[12];         // CD row pinning force input i (swing foot), or -1 (stance foot: free)
-  int puColOf[12];          // Pu column of a free force input, or -1
-#pragma unroll
-  for (int r = 0; r < NVMAX; ++r) vrOf[r] = 0;
-  {
-    int row = 0;
-#pragma unroll
-    for (int cft = 0; cft < 4; ++cft) {
-      if (contactOf(mode, cft)) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-#pragma unroll
-          for (int r = 0; r < NVMAX; ++r) if (r == nv + q) vrOf[r] = row + q;
-          frcRowOf[3 * cft + q] = -1; puColOf[3 * cft + q] = nStF + q;
-        }
-        nv += 3; nStF += 3; row += 3;
-      } else {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) { frcRowOf[3 * cft + q] = row + q; puColOf[3 * cft + q] = -1; }
-#pragma unroll
-        for (int r = 0; r < NVMAX; ++r) if (r == nv) vrOf[r] = row + 3;
-        nv += 1; row += 4;
-      }
-    }
-  }
   QM_TICK(5);
   {
     real peForce = 0.0_r;   // pinned swing-foot forces: Pe = -e_f
@@ -488,8 +412,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
       }
     }
     // publish Y (rows k < 12, my column; in region PA) and Q_v (lane 16 + c holds row c; in region X)
-    real* Ym = lds + L_YM;
-    real* Qs = lds + L_QS;
+    real* Ym = lds + LO_Y.off;
+    real* Qs = lds + LO_QV.off;
     if (lane < 32) {
 #pragma unroll
       for (int k = 0; k < NVMAX; ++k) Ym[k * LDY + lane] = lane <= 30 ? y[k] : 0.0_r;
@@ -686,7 +610,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
 #pragma unroll
           for (int ks = 0; ks < 2; ++ks) {
             const int qq = 4 * ks + h, qc2 = qq < 6 ? qq : 0;     // error row this lane supplies
-            ej[ks] = EEJ[qc2 * 32 + tn * 16 + l16]; e0[ks] = EEJ[qc2 * 32 + la]; e1[ks] = EEJ[qc2 * 32 + 16 + la];
+            ej[ks] = EEJ[qc2 * EEJ_LD + tn * 16 + l16]; e0[ks] = EEJ[qc2 * EEJ_LD + la]; e1[ks] = EEJ[qc2 * EEJ_LD + 16 + la];
           }
 #pragma unroll
           for (int ks = 0; ks < 2; ++ks) { QM_KEEP(ej[ks]); QM_KEEP(e0[ks]); QM_KEEP(e1[ks]); }

@@ -23,6 +23,7 @@
 // of W and the columns >= m~ of B~ (padded by lq_node_kernel) are exactly zero, so partial tiles need no predication.
 #pragma once
 #include "layout.h"
+#include "contact_rows.h"
 #include "gpu_rt.h"
 #include "riccati_lds.h"
 
@@ -754,7 +755,7 @@ template <int NW> __global__ void __launch_bounds__(NW * 64) QM_ONE_WAVE_PER_SIM
         const int j = k - 1;
         const real* stg = lds + RO_RING.off + slPrev * STG_F;
         const real* zv = lds + RO_ZV.off + slPrev * ZV;
-        if (wave == 1) {   // du = Pe + Px dx + Pu du~: joint rows from the chain's s, force rows from the contact mode (layout.h: puColumnOfForce)
+        if (wave == 1) {   // du = Pe + Px dx + Pu du~: joint rows from the chain's s, force rows from the contact mode (contact_rows.h: puColumnOfForce)
           if (lane < 30) {
             const int puCol = puColumnOfForce(int(stg[OFF_MODE]), lane < 12 ? lane : 0);
             const real rowPart = lane >= 12 ? zv[48 + lane] : (puCol >= 0 ? zv[30 + (puCol >= 0 ? puCol : 0)] : 0.0_r);

@@ -6,6 +6,7 @@
 // target interpolation (LeggedRobotQuadraticTrackingCost.h:37, EndEffectorConstraint.cpp:80-113).
 #pragma once
 #include "problem_r.h"
+#include "contact_rows.h"   // contactOf and the row structure of a mode
 #include "gpu_rt.h"
 
 namespace qmk {
@@ -23,7 +24,6 @@ __device__ __forceinline__ int nodePhaseAt(const Schedule& s, real t) {
   while (i < s.numEvents && s.eventTimes[i] <= t) ++i;
   return i;
 }
-__device__ __forceinline__ bool contactOf(int mode, int leg) { return (mode >> (3 - leg)) & 1; }
 
 // Hermite cubic in normalised time (upstream CubicSpline): value and time derivative at t.
 __device__ __forceinline__ void cubic(real t0, real p0, real v0, real t1, real p1, real v1, real t, real& pos, real& vel) {

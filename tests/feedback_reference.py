@@ -19,6 +19,7 @@ import scipy.sparse.linalg as spla
 
 import kkt_reference as KR
 import kkt_scenarios as KS
+from support import contact_flags
 
 EPS = np.finfo(np.float64).eps
 
@@ -116,7 +117,7 @@ def check_structure(name, out, K, uff):
             assert (gap <= bound).all(), (name, i, k, gap.max())
             mode = int(out["mode"][i, k])
             for leg in range(4):
-                if not (mode >> (3 - leg)) & 1:
+                if not contact_flags(mode)[leg]:
                     assert not K[i, k, 3 * leg:3 * leg + 3].any(), (name, i, k, leg)
     print(name, "fixed point: worst |uff + K X - U| / bound", worst)
 

@@ -62,12 +62,9 @@ def cold_iterate(itf, oracle, x0, grid, nev, ev, md):
     """the initializer's guess (QMInitializer.cpp:33-41): x_k = x0, u_k = weight compensation of the node's mode"""
     N = len(grid) - 1
     X, U = np.repeat(x0[None, :], N + 1, axis=0), np.zeros((N, 30))
-    weight = itf.robot_mass * itf.problem.settings.gravity
     for k in range(N):
         mode = oracle.node_mode_at(ev[:nev], md[:nev + 1], grid[k])
-        legs = [c for c in range(4) if (mode >> (3 - c)) & 1]
-        for c in legs:
-            U[k, 3 * c + 2] = weight / len(legs)
+        U[k] = S.nominal_input(itf.robot_mass, mode, gravity=itf.problem.settings.gravity)
     return X, U
 
 

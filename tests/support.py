@@ -376,6 +376,44 @@ def trot_schedule(t_end, period=0.70, phase0=0.0):
     return len(ev), evp, mdp
 
 
+def contact_flags(mode):
+    """stance flag per foot (LF, RF, LH, RH) of a 4-bit contact mode: the decode of csrc/kernels/contact_rows.h (contactOf)"""
+    return [(int(mode) >> (3 - c)) & 1 for c in range(4)]
+
+
+def nominal_input(mass, mode, gravity=9.81):
+    """QMInitializer's input: the weight shared by the stance feet on their z entries, nothing else (all zero in flight)"""
+    flags = contact_flags(mode)
+    u = np.zeros(30)
+    for c in range(4):
+        if flags[c]:
+            u[3 * c + 2] = mass * gravity / max(1, sum(flags))
+    return u
+
+
+def check_lq_blocks_of_every_contact_mode(itf, oracle, solve):
+    """The un-projected LQ blocks of all sixteen contact modes against oracle.lq_node: the swing feet's zero-force rows are synthesised by lq_node_kernel from the mode
+    (csrc/kernels/contact_rows.h), not loaded, and only trot (9, 6, 15) is reached by the other debug_lq comparisons.  Instance m holds mode m over the whole
+    horizon (its only event lies twenty horizons ahead).  solve(B, N, x0, tt, ts, nev, ev, md) runs one MPC call with the debug dump on and returns the solver."""
+    B, N = 16, 2
+    dt = itf.problem.settings.dt
+    x0 = perturbed_states(itf.initial_state, B, seed=0)
+    tt = np.zeros((B, 1)); ts = np.tile(nominal_target(oracle, itf.initial_state), (B, 1, 1)).copy()
+    nev = np.ones(B, dtype=np.int32)
+    ev = np.full((B, abi.MAX_EVENTS), 1e300); ev[:, 0] = 20 * N * dt
+    md = np.full((B, abi.MAX_EVENTS + 1), 15, dtype=np.int32); md[:, 0] = np.arange(B)
+    sol = solve(B, N, x0, tt, ts, nev, ev, md)
+    for mode in range(B):
+        for k in (0, 1, N):
+            g = sol.debug_lq(mode, k)
+            assert oracle.node_mode_at(ev[mode, :1], md[mode, :2], k * dt) == mode
+            u = nominal_input(itf.robot_mass, mode)
+            o = oracle.lq_node(k * dt, dt if k < N else 0.0, x0[mode], u if k < N else None, x0[mode], k == N, 1, ev[mode], md[mode], tt[mode], ts[mode])
+            assert g["nc"] == o["nc"] == (0 if k == N else sum(3 if f else 4 for f in contact_flags(mode))), (mode, k)
+            for key in (["Q", "q"] if k == N else ["A", "B", "b", "Q", "R", "q", "r", "C", "D", "e"]):
+                assert np.abs(g[key] - o[key]).max() <= 1e-10 * max(1.0, np.abs(o[key]).max()), (mode, k, key)
+
+
 def nominal_target(oracle, x_nom):
     _, _, ee, eq, _ = oracle.kinematics(x_nom, np.zeros(30))
     return np.r_[x_nom, ee, eq]
@@ -481,10 +519,8 @@ def relaxed_barrier_batch(interface, oracle, B=4, N=12):
     for i in range(B):
         for k in range(N):
             mode = oracle.node_mode_at(ev[:nev], md[:nev + 1], k * dt)
-            flags = [(mode >> (3 - c)) & 1 for c in range(4)]
-            st = [c for c in range(4) if flags[c]]
-            for c in st:
-                U[i, k, 3 * c + 2] = m * 9.81 / len(st)
+            st = [c for c in range(4) if contact_flags(mode)[c]]
+            U[i, k] = nominal_input(m, mode)
             U[i, k, 3 * st[0] + 2] = 3.0 + i                    # h = 0.7 * 3 - 5 < delta: quadratic branch
             U[i, k, 3 * st[0]] = 4.0
             if i == 3:
@@ -511,10 +547,7 @@ def wbc_stress_batch(interface, variant, B=2048):
     vm = rng.uniform(-1, 1, (B, 24)) * 0.1
     u = np.zeros((B, 30))
     for i in range(B):
-        flags = [(int(mode[i]) >> (3 - c)) & 1 for c in range(4)]
-        for c in range(4):
-            if flags[c]:
-                u[i, 3 * c + 2] = m * 9.81 / max(1, sum(flags))
+        u[i] = nominal_input(m, mode[i])
     u[:, :12] += rng.uniform(-1, 1, (B, 12)) * 2.0 * (u[:, :12] != 0)
     u[:, 12:] = rng.uniform(-1, 1, (B, 18)) * 0.1
     il = u + rng.uniform(-1, 1, (B, 30)) * 0.002

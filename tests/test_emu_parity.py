@@ -37,11 +37,7 @@ def test_emu_lq_and_sqp_iteration(emu):
         for k in (0, 3, N):
             g = sol.debug_lq(inst, k)
             mode = orc.node_mode_at(ev[:nev], md[:nev + 1], k * dt)
-            flags = [(mode >> (3 - c)) & 1 for c in range(4)]
-            u = np.zeros(30)
-            for c in range(4):
-                if flags[c]:
-                    u[3 * c + 2] = itf.robot_mass * 9.81 / sum(flags)
+            u = S.nominal_input(itf.robot_mass, mode)
             o = orc.lq_node(k * dt, dt if k < N else 0.0, x0[inst], u if k < N else None, x0[inst], k == N, nev, ev, md, tt[inst], ts[inst])
             assert g["nc"] == o["nc"]
             for key in (["Q", "q"] if k == N else ["A", "B", "b", "Q", "R", "q", "r", "C", "D", "e"]):
@@ -51,6 +47,18 @@ def test_emu_lq_and_sqp_iteration(emu):
         assert np.abs(oX[inst] - ref["X"]).max() <= 1e-8 * max(1.0, np.abs(ref["X"]).max())
         assert np.abs(oU[inst] - ref["U"]).max() <= 1e-8 * max(1.0, np.abs(ref["U"]).max())
         assert np.allclose(oS[inst][:7], ref["stats"][:7], rtol=1e-8, atol=1e-10)
+
+
+def test_lq_blocks_of_every_contact_mode(emu):
+    itf, orc = emu
+
+    def solve(B, N, x0, tt, ts, nev, ev, md):
+        sol = api.GpuSolver(itf, max_batch=B, max_nodes=N)
+        sol.enable_debug(True)
+        out = np.zeros((B, N + 1)), np.zeros((B, N + 1, 30)), np.zeros((B, N, 30)), np.zeros((B, N + 1), dtype=np.int32), np.zeros((B, abi.NSTATS))
+        sol.mpc(sol.mpc_args(B, N, x0, tt, ts, nev, ev, md, *out, t0=np.zeros(B)))
+        return sol
+    S.check_lq_blocks_of_every_contact_mode(itf, orc, solve)
 
 
 def test_emu_line_search_launch_shape_for_batches_beyond_the_cus(emu):
@@ -84,11 +92,7 @@ def test_emu_wbc(emu):
     x_nom, m = itf.initial_state, itf.robot_mass
     cases = []
     for mode, t in ((9, 20.0), (15, 5.0)):
-        flags = [(mode >> (3 - c)) & 1 for c in range(4)]
-        u = np.zeros(30)
-        for c in range(4):
-            if flags[c]:
-                u[3 * c + 2] = m * 9.81 / sum(flags)
+        u = S.nominal_input(m, mode)
         u[12:] = rng.uniform(-1, 1, 18) * 0.05
         xd = x_nom + rng.uniform(-1, 1, 30) * 0.02
         rbd = S.rbd_from_state(orc, x_nom + rng.uniform(-1, 1, 30) * 0.01, rng.uniform(-1, 1, 24) * 0.05)
@@ -256,10 +260,8 @@ def test_emu_sqp_convergence_test_skips_converged_instances():
     wx = np.stack([solved["X"], np.tile(x0[1], (N + 1, 1))]); wu = np.stack([solved["U"], cold["U"] * 0.0])
     for k in range(N):
         mode = orc.node_mode_at(ev[:nev], md[:nev + 1], k * itf.problem.settings.dt)
-        flags = [(mode >> (3 - c)) & 1 for c in range(4)]
-        for c in range(4):
-            if flags[c]:
-                wu[1, k, 3 * c + 2] = itf.robot_mass * 9.81 / sum(flags)
+        fz = wu[1, k, 2:12:3]   # (a view: only the stance feet's entries are written, the rest keeps cold U * 0.0)
+        fz[:] = np.where(S.contact_flags(mode), S.nominal_input(itf.robot_mass, mode)[2:12:3], fz)
     sol = api.GpuSolver(itf, max_batch=B, max_nodes=N)
     oT, oX, oU, oM, oS = np.zeros((B, N + 1)), np.zeros((B, N + 1, 30)), np.zeros((B, N, 30)), np.zeros((B, N + 1), dtype=np.int32), np.zeros((B, abi.NSTATS))
     a = sol.mpc_args(B, N, x0, tt, ts, np.full(B, nev, dtype=np.int32), np.tile(ev, (B, 1)).copy(), np.tile(md, (B, 1)).copy(), oT, oX, oU, oM, oS, t0=np.zeros(B),

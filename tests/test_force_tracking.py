@@ -72,11 +72,7 @@ def test_emu_force_tracking_matches_oracle():
         for k in (1, 4):
             g = sol.debug_lq(inst, k)
             mode = orc.node_mode_at(ev[:nev], md[:nev + 1], k * dt)
-            flags = [(mode >> (3 - c)) & 1 for c in range(4)]
-            u = np.zeros(30)
-            for c in range(4):
-                if flags[c]:
-                    u[3 * c + 2] = itf.robot_mass * 9.81 / sum(flags)
+            u = S.nominal_input(itf.robot_mass, mode)
             o = orc.lq_node(k * dt, dt, x0[inst], u, x0[inst], False, nev, ev, md, tt[inst], ts[inst])
             for key in ("A", "B", "b", "Q", "R", "q", "r", "C", "D", "e"):
                 assert np.abs(g[key] - o[key]).max() <= 1e-10 * max(1.0, np.abs(o[key]).max()), (inst, k, key)

@@ -31,16 +31,25 @@ def test_lq_blocks_match_oracle(interface, oracle):
         for k in (0, 2, 3, N):
             g = sol.debug_lq(inst, k)
             mode = oracle.node_mode_at(ev[:nev], md[:nev + 1], k * dt)
-            flags = [(mode >> (3 - c)) & 1 for c in range(4)]
-            u = np.zeros(30)
-            for c in range(4):
-                if flags[c]:
-                    u[3 * c + 2] = interface.robot_mass * 9.81 / sum(flags)
+            u = S.nominal_input(interface.robot_mass, mode)
             o = oracle.lq_node(k * dt, dt if k < N else 0.0, x0[inst], u if k < N else None, x0[inst], k == N, nev, ev, md, tt[inst], ts[inst])
             assert g["nc"] == o["nc"]
             for key in (["Q", "q"] if k == N else ["A", "B", "b", "Q", "R", "q", "r", "C", "D", "e"]):
                 scale = max(1.0, np.abs(o[key]).max())
                 assert np.abs(g[key] - o[key]).max() <= 1e-10 * scale, (inst, k, key)
+
+
+def test_lq_blocks_of_every_contact_mode(interface, oracle):
+    import gpu_harness as G
+
+    def solve(B, N, x0, tt, ts, nev, ev, md):
+        sol = G.make_solver(interface, B, N)
+        sol.enable_debug(True)
+        mb = G.MpcBatch(x0, tt, ts, nev, ev, md, N)
+        sol.mpc(mb.args)
+        mb.results()
+        return sol
+    S.check_lq_blocks_of_every_contact_mode(interface, oracle, solve)
 
 
 @pytest.mark.parametrize("N,B", [(20, 3), (100, 2)])

@@ -12,11 +12,7 @@ def _cases(interface, oracle, variant, seed=3):
     x_nom, m = interface.initial_state, interface.robot_mass
     out = []
     for mode, t in ((15, 20.0), (15, 5.0), (9, 20.0), (6, 12.0), (0, 20.0), (13, 20.0), (7, 20.0), (10, 20.0)):
-        flags = [(mode >> (3 - c)) & 1 for c in range(4)]
-        u = np.zeros(30)
-        for c in range(4):
-            if flags[c]:
-                u[3 * c + 2] = m * 9.81 / max(1, sum(flags))
+        u = S.nominal_input(m, mode)
         u[12:] = rng.uniform(-1, 1, 18) * 0.05
         xd = x_nom + rng.uniform(-1, 1, 30) * 0.02
         xm = x_nom + rng.uniform(-1, 1, 30) * 0.01

@@ -153,7 +153,7 @@ def test_event_node_switches_constraint_rows(interface, oracle):
     k = int(np.argmin(np.abs(grid - ev[0])))
     assert grid[k] == ev[0]
     assert r["mode"][k - 1] == md[0] and r["mode"][k] == md[1] and md[0] != md[1]
-    nc = lambda m: sum(3 if (m >> (3 - c)) & 1 else 4 for c in range(4))
+    nc = lambda m: sum(3 if f else 4 for f in S.contact_flags(m))
     lq = oracle.lq_node(grid[k], grid[k + 1] - grid[k], r["X"][k], r["U"][k], r["X"][k + 1], False, nev, ev, md, np.zeros(1), tgt[None, :].copy())
     assert lq["nc"] == nc(int(md[1]))
 
@@ -280,11 +280,7 @@ def test_riccati_step_equals_dense_kkt_solve(interface, oracle):
     lq = []
     for k in range(N + 1):
         mode = oracle.node_mode_at(ev[:nev], md[:nev + 1], k * dt)
-        flags = [(mode >> (3 - c)) & 1 for c in range(4)]
-        u = np.zeros(30)
-        for c in range(4):
-            if flags[c]:
-                u[3 * c + 2] = m * 9.81 / sum(flags)
+        u = S.nominal_input(m, mode)
         lq.append((oracle.lq_node(k * dt, dt if k < N else 0.0, x0, u if k < N else None, x0, k == N, nev, ev, md, tt, ts), u))
     nz = 30 * (N + 1) + 30 * N
     ix = lambda k: slice(30 * k, 30 * k + 30)
@@ -374,11 +370,10 @@ def test_full_size_hoqp_levels_against_a_primal_active_set_method(interface, ora
     x_nom, m = interface.initial_state, interface.robot_mass
     checked = undecided = 0
     for mode in (15, 9, 6, 10, 5, 13, 7, 14, 11, 0):
-        flags = [(mode >> (3 - c)) & 1 for c in range(4)]
-        u = np.zeros(30)
+        u = S.nominal_input(m, mode)
         for c in range(4):
-            if flags[c]:
-                u[3 * c:3 * c + 3] = [rng.uniform(-8, 8), rng.uniform(-8, 8), m * 9.81 / max(1, sum(flags))]
+            if S.contact_flags(mode)[c]:
+                u[3 * c:3 * c + 2] = [rng.uniform(-8, 8), rng.uniform(-8, 8)]
         u[12:] = rng.uniform(-1, 1, 18) * 0.1
         xd = x_nom + rng.uniform(-1, 1, 30) * 0.02
         rbd = S.rbd_from_state(oracle, x_nom + rng.uniform(-1, 1, 30) * 0.01, rng.uniform(-1, 1, 24) * 0.05)

@@ -3,7 +3,7 @@
 
 Everything the oracle and the kernels know about the robot reaches them through the product's URDF loader (qmgpu_load_problem) and their own
 recursive / Jacobian-sum formulations.  This script shares NOTHING with either:
-  * it parses qm_door_amd/data/aliengo_z1.urdf itself (xml.etree), keeps all 28 links as separate bodies (no merging of fixed children),
+  * it parses qm_door_amd/data/aliengo_z1.urdf itself (xml.etree, tests/urdf_model.py), keeps all 28 links as separate bodies (no merging of fixed children),
   * forward kinematics is the only geometry it implements; body velocities come from COMPLEX-STEP differentiation of that forward kinematics
     (exact to round-off), never from a geometric Jacobian formula,
   * the mass matrix is the Hessian of the kinetic energy T(q, v) = 1/2 sum_b (m_b |v_b|^2 + w_b^T R_b I_b R_b^T w_b) in v,
@@ -16,67 +16,15 @@ v = dq/dt (Euler ZYX rates).  The gripper joint is held at 0 (the reference's mo
 Run:  python tests/golden/make_model_fixture.py      (a few seconds; numpy only)
 tests/test_oracle_invariants.py::test_model_against_independent_fixture compares the oracle with the result."""
 import os
-import xml.etree.ElementTree as ET
+import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-URDF = os.path.join(HERE, "..", "..", "qm_door_amd", "data", "aliengo_z1.urdf")
-JOINT_ORDER = [f"{leg}_{j}" for leg in ("LF", "LH", "RF", "RH") for j in ("HAA", "HFE", "KFE")] + [f"z1_joint_{i}" for i in range(1, 7)]
+sys.path.insert(0, os.path.join(HERE, ".."))
+from urdf_model import LINKS, fk  # noqa: E402  (the parser and the forward kinematics: tests/urdf_model.py, shared with tests/lq_reference.py)
+
 G = 9.81
-
-
-def parse():
-    root = ET.parse(URDF).getroot()
-    links = {}
-    for l in root.findall("link"):
-        inert = l.find("inertial")
-        if inert is None:
-            links[l.get("name")] = dict(m=0.0, c=np.zeros(3), I=np.zeros((3, 3)))
-            continue
-        i = inert.find("inertia")
-        I = np.array([[float(i.get("ixx")), float(i.get("ixy")), float(i.get("ixz"))], [float(i.get("ixy")), float(i.get("iyy")), float(i.get("iyz"))],
-                      [float(i.get("ixz")), float(i.get("iyz")), float(i.get("izz"))]])
-        assert inert.find("origin").get("rpy").split() == ["0", "0", "0"]
-        links[l.get("name")] = dict(m=float(inert.find("mass").get("value")), c=np.array(inert.find("origin").get("xyz").split(), float), I=I)
-    joints = []
-    for j in root.findall("joint"):
-        o = j.find("origin")
-        assert [float(t) for t in o.get("rpy").split()] == [0.0, 0.0, 0.0]
-        ax = j.find("axis")
-        joints.append(dict(name=j.get("name"), type=j.get("type"), parent=j.find("parent").get("link"), child=j.find("child").get("link"),
-                           xyz=np.array(o.get("xyz").split(), float), axis=None if ax is None else np.array(ax.get("xyz").split(), float)))
-    return links, joints
-
-
-LINKS, JOINTS = parse()
-CHILDREN = {}
-for jt in JOINTS:
-    CHILDREN.setdefault(jt["parent"], []).append(jt)
-
-
-def rot(axis, a):
-    """Rodrigues rotation about a unit axis; works for complex angles (complex step)."""
-    x, y, z = axis
-    K = np.array([[0, -z, y], [z, 0, -x], [-y, x, 0]], dtype=complex)
-    return np.eye(3, dtype=complex) + np.sin(a) * K + (1 - np.cos(a)) * (K @ K)
-
-
-def fk(q):
-    """world pose (R, p) of every link for generalised coordinates q (possibly complex)."""
-    q = np.asarray(q, dtype=complex)
-    R0 = rot((0, 0, 1), q[3]) @ rot((0, 1, 0), q[4]) @ rot((1, 0, 0), q[5])
-    pose = {"base": (R0, q[0:3].copy())}
-    stack = ["base"]
-    while stack:
-        parent = stack.pop()
-        Rp, pp = pose[parent]
-        for jt in CHILDREN.get(parent, []):
-            ang = q[6 + JOINT_ORDER.index(jt["name"])] if jt["name"] in JOINT_ORDER else 0.0
-            Rc = Rp @ rot(jt["axis"], ang) if jt["type"] == "revolute" else Rp
-            pose[jt["child"]] = (Rc, pp + Rp @ jt["xyz"])
-            stack.append(jt["child"])
-    return pose
 
 
 H = 1e-30

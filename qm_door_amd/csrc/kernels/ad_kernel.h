@@ -24,6 +24,7 @@
 // Output: the AD rows of lq_kernel.h (one 64-double row per differentiated scalar: entries < 60 the derivative along (x, u), entry
 // 60 the value) -- unchanged, lq_node_kernel does not know how they were produced.
 #pragma once
+#include "ad_lds.h"   // the kernel's lanes per node, nodes per wavefront and LDS
 #include "layout.h"
 #include "schedule_dev.h"
 #include "sweep_dev.h"
@@ -56,13 +57,13 @@ struct LqArgs {
 };
 
 // AD rows: one 64-double row per differentiated scalar; entry l < 60 = d/d(x,u)_l, entry 60 = the value itself
-constexpr int AD_PHI = 0;                    // [12] RK2 increment phi = dt/2 (k1 + k2) of the momentum / base-pose states
-constexpr int AD_CD = AD_PHI + 12 * 64;      // [16] equality constraint rows
-constexpr int AD_EE = AD_CD + 16 * 64;       // [6]  end-effector pose error
-constexpr int AD_DOUBLES = AD_EE + 6 * 64;   // 2176
+constexpr int AD_ROW_LD = 64;
+constexpr int AD_PHI = 0;                           // [12] RK2 increment phi = dt/2 (k1 + k2) of the momentum / base-pose states
+constexpr int AD_CD = AD_PHI + 12 * AD_ROW_LD;      // [16] equality constraint rows
+constexpr int AD_EE = AD_CD + 16 * AD_ROW_LD;       // [6]  end-effector pose error
+constexpr int AD_DOUBLES = AD_EE + 6 * AD_ROW_LD;   // 2176
+static_assert(AD_J_LD == AD_ROW_LD, "the Jacobian rows in LDS (ad_lds.h) are AD rows: putRow, and the phi rows leave column for column");
 
-constexpr int AD_DIRS = 21;                  // configuration directions = lanes per node
-constexpr int AD_NODES = 3;                  // nodes per wavefront
 __host__ __device__ constexpr int adGridFor(int nodes) { return (nodes + AD_NODES - 1) / AD_NODES; }
 
 // Inputs of the sweep as seen by one lane: values from the node's x | u staged in LDS, seeds from the lane's direction.
@@ -80,17 +81,6 @@ struct AdIn {
     return Vec3<Du3>(Du3(u[3 * c], 0.0_r, dd == 6 + 3 * c ? 1.0_r : 0.0_r), Du3(u[3 * c + 1], 0.0_r, dd == 7 + 3 * c ? 1.0_r : 0.0_r), Du3(u[3 * c + 2], 0.0_r, dd == 8 + 3 * c ? 1.0_r : 0.0_r));
   }
 };
-
-// LDS of one wavefront (doubles): 37 KiB, four wavefronts (one per SIMD: the sweep needs the whole register file) per CU
-constexpr int ADL_XU = 0;                              // [3][64]  x (0..29) | u (32..61) per node
-constexpr int ADL_X2 = ADL_XU + AD_NODES * 64;         // [3][12]  x + dt k1, momentum / base-pose part
-constexpr int ADL_A2 = ADL_X2 + AD_NODES * 12;         // [3][12][16] J2[:, 0:12] (operand of the chain-rule product), columns 12..15 zero
-constexpr int ADL_PARK = ADL_A2 + AD_NODES * 12 * 16;  // feet of the first stage [4][15][64]  /  J1 then J1 + J2 + ... [3][12][64]
-constexpr int AD_PARK_DOUBLES = 4 * 15 * 64;
-constexpr int ADL_PUB = ADL_PARK + AD_PARK_DOUBLES;    // [3][119] primal composites of the five kinematic chains of each node (sweep_dev.h: centroidalSweepOwnChain)
-constexpr int AD_LDS_DOUBLES = ADL_PUB + AD_NODES * SWEEP_PUB_NODE;
-static_assert(AD_NODES * 12 * 64 <= AD_PARK_DOUBLES, "the Jacobian rows reuse the parking area");
-static_assert(AD_LDS_DOUBLES * sizeof(real) <= 40960, "four wavefronts per CU");
 
 #ifndef QM_LQ_UNIT   // (qmgpu_lq.hip includes this file for LqArgs and the row layout only)
 __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs a) {
@@ -117,11 +107,11 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
   const bool isF = dd >= 3 && dd < 18, isVal = dd == 18;   // lanes whose closed-form column is a force-type slot (p only matters with the EE contact)
 
   real* ad = a.adrows + size_t(gnode) * AD_DOUBLES;
-  real* xu = lds + ADL_XU + grp * 64;
-  real* x2 = lds + ADL_X2 + grp * 12;
-  real* A2 = lds + ADL_A2 + grp * 192;
-  real* park = lds + ADL_PARK + lane;                 // lane-private columns while the feet wait for the base twist
-  real* L1 = lds + ADL_PARK + grp * 768;              // [12][64] Jacobian rows of this node
+  real* xu = lds + ADL_XU.off + grp * AD_XU_LD;
+  real* x2 = lds + ADL_X2.off + grp * AD_X2_NODE;
+  real* A2 = lds + ADL_A2.off + grp * AD_A2_NODE;
+  real* park = lds + ADL_PARK.off + lane;             // lane-private columns while the feet wait for the base twist
+  real* L1 = lds + ADL_J.off + grp * AD_J_NODE;       // [12][AD_J_LD] Jacobian rows of this node
 
   const real* tg = a.tgrid + size_t(inst) * (a.N + 1);
   const real t = tg[node];
@@ -129,10 +119,10 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
   {  // x | u of the three nodes: lanes dd load 30 + 30 values of their node
     const real* xG = a.X + size_t(gnode) * 30;
     const real* uG = terminal ? a.zeros : a.U + (size_t(inst) * a.N + node) * 30;
-    for (int i = dd; i < 30; i += AD_DIRS) { xu[i] = xG[i]; xu[32 + i] = uG[i]; }
+    for (int i = dd; i < 30; i += AD_DIRS) { xu[i] = xG[i]; xu[AD_XU_U + i] = uG[i]; }
   }
   QM_WAVE_SYNC();
-  const real* x = xu; const real* u = xu + 32;
+  const real* x = xu; const real* u = xu + AD_XU_U;
   const Schedule sched{a.schedNum[inst], a.schedTimes + size_t(inst) * QMGPU_MAX_EVENTS, a.schedModes + size_t(inst) * (QMGPU_MAX_EVENTS + 1)};
   const int phase = a.nodePhase[gnode];
   const int mode = sched.modes[phase];
@@ -145,7 +135,7 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
   // one row of the AD format: the lane's configuration slot, its velocity / force slot and its closed-form column
   const bool owner = lane < AD_NODES * AD_DIRS;   // lane 63 computes along with the others but owns no column
   auto putRow = [&](real* dst, int row, real dval, real vval, real cval) {
-    real* r = dst + row * 64;
+    real* r = dst + row * AD_J_LD;
     if (owner) { r[cD] = dval; r[cV] = vval; r[cC] = cval; }
   };
   // rows that leave for HBM: streaming (non-temporal) stores -- 51 KB per workgroup that nothing on this CU reads again must not push the 2.9 KB of model
@@ -153,7 +143,7 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
   // stateOnly: a row that does not depend on the inputs (the end-effector pose error): its columns 30..59 are identically zero, lq_node_kernel does not read them
   // and they are not written (one of the four 128-byte lines of the row never exists)
   auto putGlobal = [&](int base, int row, real dval, real vval, real cval, bool stateOnly = false) {
-    real* r = ad + base + row * 64;
+    real* r = ad + base + row * AD_ROW_LD;
     if (live && owner) {
       QM_STREAM_STORE(&r[cD], dval);
       if (!stateOnly || cV < 30) QM_STREAM_STORE(&r[cV], vval);
@@ -178,11 +168,7 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
     auto footCb =
         [&](int c, Vec3<Du> r, Vec3<Du3> v) {
           QM_TICK(stage ? 3 : 1);
-          if (stage == 0) {
-            real* p = park + (c * 15) * 64;
-            p[0] = r.x.v; p[64] = r.x.d; p[128] = r.y.v; p[192] = r.y.d; p[256] = r.z.v; p[320] = r.z.d;
-            p[384] = v.x.v; p[448] = v.x.d; p[512] = v.x.e; p[576] = v.y.v; p[640] = v.y.d; p[704] = v.y.e; p[768] = v.z.v; p[832] = v.z.d; p[896] = v.z.e;
-          }
+          if (stage == 0) parkFoot(park + c * AD_PARK_FOOT, r, v);
           QM_TICK(7);
         };
     auto eeCb =
@@ -222,7 +208,7 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
           QM_TICK(8);
           return fe;
         };
-    real* pubN = lds + ADL_PUB + grp * SWEEP_PUB_NODE;
+    real* pubN = lds + ADL_PUB.off + grp * SWEEP_PUB_NODE;
     centroidalSweepOwnChain(md, st.gravity, in, dd, pubN, footCb, eeCb, f, bm);
     QM_TICK(stage ? 3 : 1);
     if (stage == 0) {
@@ -231,9 +217,9 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
 #pragma unroll 1
         for (int c = 0; c < 4; ++c) {
           const bool contact = contactOf(mode, c);
-          const real* p = park + (c * 15) * 64;
-          const Vec3<Du> r(Du(p[0], p[64]), Du(p[128], p[192]), Du(p[256], p[320]));
-          const Vec3<Du3> vj(Du3(p[384], p[448], p[512]), Du3(p[576], p[640], p[704]), Du3(p[768], p[832], p[896]));
+          Vec3<Du> r;
+          Vec3<Du3> vj;
+          parkedFoot(park + c * AD_PARK_FOOT, r, vj);
           const Vec3<Du3> vf = bm.dp + cross(bm.omega, r) + vj;
           // velocity-type row: d/dh_lin = identity through dp; d/dp_z only through the position-error gain
           auto putVel = [&](int row, Du3 hv, int axisIdx, real gainZ) {
@@ -252,7 +238,7 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
           }
         }
       }
-      QM_WAVE_SYNC();   // every lane has read its parked feet: the area becomes the Jacobian rows
+      QM_WAVE_SYNC();   // PARK is dead, its guest J begins (ad_lds.h)
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
         putRow(L1, i, f.lin[i].d, 0.0_r, isF ? f.lin[i].e : (isVal ? f.lin[i].v : 0.0_r));
@@ -262,7 +248,7 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
       for (int i = 0; i < 6; ++i) putRow(L1, 6 + i, f.kin[i].d, f.kin[i].e, isVal ? f.kin[i].v : ((i < 3 && dd == i) ? 1.0_r : 0.0_r));
       if (dd == 19) {   // the columns nobody owns: p (f does not depend on the base position) and padding 63
 #pragma unroll
-        for (int i = 0; i < 12; ++i) L1[i * 64 + 63] = 0.0_r;
+        for (int i = 0; i < 12; ++i) L1[i * AD_J_LD + AD_J_LD - 1] = 0.0_r;
       }
       if (dd == 0) {
 #pragma unroll
@@ -279,16 +265,16 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
         for (int i = 0; i < 12; ++i) {
           const real dv = i < 3 ? f.lin[i].d : (i < 6 ? f.ang[i - 3].d : f.kin[i - 6].d);
           const real vv = i < 6 ? 0.0_r : f.kin[i - 6].e;
-          A2[i * 16 + dd] = (i >= 6 && i < 9 && i - 6 == dd) ? 1.0_r : 0.0_r;   // d/dh_lin
-          A2[i * 16 + 3 + dd] = vv;                                          // d/dh_ang
-          A2[i * 16 + 9 + dd] = dv;                                          // d/dzyx
-          A2[i * 16 + 12 + dd] = 0.0_r;
+          A2[i * AD_A2_LD + dd] = (i >= 6 && i < 9 && i - 6 == dd) ? 1.0_r : 0.0_r;   // d/dh_lin
+          A2[i * AD_A2_LD + 3 + dd] = vv;                                          // d/dh_ang
+          A2[i * AD_A2_LD + 9 + dd] = dv;                                          // d/dzyx
+          A2[i * AD_A2_LD + 12 + dd] = 0.0_r;
         }
       } else if (dd < 6) {   // d/dp: only the contact force of the force-tracking formulation depends on the base position
 #pragma unroll
         for (int i = 0; i < 12; ++i) {
-          A2[i * 16 + 3 + dd] = i < 3 ? f.lin[i].e : (i < 6 ? f.ang[i - 3].e : 0.0_r);
-          if (dd == 3) A2[i * 16 + 15] = 0.0_r;
+          A2[i * AD_A2_LD + 3 + dd] = i < 3 ? f.lin[i].e : (i < 6 ? f.ang[i - 3].e : 0.0_r);
+          if (dd == 3) A2[i * AD_A2_LD + 15] = 0.0_r;
         }
       }
       QM_WAVE_SYNC();
@@ -296,17 +282,17 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
       QmAcc acc[AD_NODES][4];
 #pragma unroll
       for (int g = 0; g < AD_NODES; ++g) {
-        const real* A2g = lds + ADL_A2 + g * 192;
-        const real* L1g = lds + ADL_PARK + g * 768;
+        const real* A2g = lds + ADL_A2.off + g * AD_A2_NODE;
+        const real* L1g = lds + ADL_J.off + g * AD_J_NODE;
         real av[3];
 #pragma unroll
-        for (int ks = 0; ks < 3; ++ks) { const real raw = A2g[(la < 12 ? la : 0) * 16 + 4 * ks + h]; av[ks] = la < 12 ? raw : 0.0_r; }
+        for (int ks = 0; ks < 3; ++ks) { const real raw = A2g[(la < 12 ? la : 0) * AD_A2_LD + 4 * ks + h]; av[ks] = la < 12 ? raw : 0.0_r; }
 #pragma unroll
         for (int tn = 0; tn < 4; ++tn) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) acc[g][tn][r] = 0.0_r;
 #pragma unroll
-          for (int ks = 0; ks < 3; ++ks) qmMfma(acc[g][tn], av[ks], L1g[(4 * ks + h) * 64 + tn * 16 + l16]);
+          for (int ks = 0; ks < 3; ++ks) qmMfma(acc[g][tn], av[ks], L1g[(4 * ks + h) * AD_J_LD + tn * 16 + l16]);
         }
       }
       QM_WAVE_SYNC();   // J1 has been read by every lane: the slot owners add J2 (+ dt J2[:, q_j] into the v_j columns) in place
@@ -327,11 +313,11 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
         if (owner) {
           real a0[12], a1[12], a2[12];
 #pragma unroll
-          for (int row = 0; row < 12; ++row) { const real* r = L1 + row * 64; a0[row] = r[cD]; a1[row] = r[cV]; a2[row] = r[cC]; }
+          for (int row = 0; row < 12; ++row) { const real* r = L1 + row * AD_J_LD; a0[row] = r[cD]; a1[row] = r[cV]; a2[row] = r[cC]; }
 #pragma unroll
           for (int row = 0; row < 12; ++row) { QM_KEEP(a0[row]); QM_KEEP(a1[row]); QM_KEEP(a2[row]); }
 #pragma unroll
-          for (int row = 0; row < 12; ++row) { real* r = L1 + row * 64; r[cD] = a0[row] + dv[row]; r[cV] = a1[row] + fma(sh, dv[row], vv[row]); r[cC] = a2[row] + cv[row]; }
+          for (int row = 0; row < 12; ++row) { real* r = L1 + row * AD_J_LD; r[cD] = a0[row] + dv[row]; r[cV] = a1[row] + fma(sh, dv[row], vv[row]); r[cC] = a2[row] + cv[row]; }
         }
       }
       QM_WAVE_SYNC();
@@ -345,17 +331,17 @@ __global__ void __launch_bounds__(64) QM_ONE_WAVE_PER_SIMD ad_node_kernel(LqArgs
         const bool termG = nodeG == a.N;
         const bool liveG = gR < total && !a.done[instG];
         const real dtG = a.dtgrid[gN];
-        const real* L1g = lds + ADL_PARK + g * 768;
+        const real* L1g = lds + ADL_J.off + g * AD_J_NODE;
         real* adG = a.adrows + size_t(gN) * AD_DOUBLES;
 #pragma unroll
         for (int tn = 0; tn < 4; ++tn) {
 #pragma unroll
           for (int r = 0; r < 3; ++r) {
             const int i = h + 4 * r, c = tn * 16 + l16;
-            const real s = L1g[i * 64 + c];
+            const real s = L1g[i * AD_J_LD + c];
             // terminal node: the slope itself (one stage); otherwise dt/2 (J1 + J2 + dt J2x J1), the value column without the product
             const real v = termG ? 0.5_r * s : 0.5_r * dtG * (c < 60 ? fma(dtG, acc[g][tn][r], s) : s);
-            if (liveG) QM_STREAM_STORE(&adG[AD_PHI + i * 64 + c], v);
+            if (liveG) QM_STREAM_STORE(&adG[AD_PHI + i * AD_ROW_LD + c], v);
           }
         }
       }

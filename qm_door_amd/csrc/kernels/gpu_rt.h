@@ -190,7 +190,8 @@ __device__ __forceinline__ int qmOpaqueLane(int v) { asm volatile("" : "+v"(v));
 #define QM_POISON_LDS(ptr, count)   // host emulation only: fills LDS with NaN at kernel start
 #define QM_LAUNCH(kernel, grid, block, stream, ...) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__)
 #define QM_LAUNCH_DYN(kernel, grid, block, shmemBytes, stream, ...) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), shmemBytes, stream, __VA_ARGS__)
-// dynamic LDS (keeps the base 16-byte aligned: no static __shared__ may precede it in the same kernel)
+// dynamic LDS.  It begins behind the kernel's static __shared__ objects (.group_segment_fixed_size of the code object), at the next multiple of the 16 bytes declared
+// here; a kernel that has both (linesearch_kernel) is launched with its dynamic bytes only and has to count the static ones into the CU's budget itself (ls_lds.h)
 #define QM_DYNAMIC_LDS(name) extern __shared__ __attribute__((aligned(16))) qmk::real name[]
 #define QM_ALLOW_DYNAMIC_LDS(kernel, bytes) hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes)
 #endif

@@ -45,6 +45,9 @@ constexpr int GAIN_DOUBLES = MT * 30 + MT + 2;  // 560
 //   log(delta) of the joint-position, joint-velocity and friction-cone barrier; value(-lower) + value(upper) per arm joint for positions and velocities
 constexpr int QM_RW_DERIVED = 900, QM_BC_LOGD_POS = 0, QM_BC_LOGD_VEL = 1, QM_BC_LOGD_FRIC = 2, QM_BC_POS0 = 4, QM_BC_VEL0 = 10, QM_RW_DOUBLES = 916;
 
+// LDS of one compute unit (gfx950): what the LDS carves divide among the workgroups of a CU (ad_lds.h, lq_lds.h, ls_lds.h) and what a launch may ask for at most
+constexpr int QM_CU_LDS_BYTES = 160 * 1024;
+
 // per-node metrics: dt*cost, dt*|defect|^2, dt*|eq|^2, armijo contribution (filled by the forward sweep)
 constexpr int NODE_METRICS = 4;
 

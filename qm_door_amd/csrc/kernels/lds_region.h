@@ -1,4 +1,5 @@
-// lds_region.h -- a region of a kernel's dynamic LDS, for the carves that declare every region once (wbc_lds.h, riccati_lds.h).
+// lds_region.h -- a region of a kernel's LDS array, for the carves that declare every region once: wbc_lds.h, riccati_lds.h (dynamic LDS), lq_lds.h, ad_lds.h (one static
+// array).  ls_lds.h, the fifth map, names the separate __shared__ arrays of linesearch_kernel and needs no regions.
 #pragma once
 
 namespace qmk {

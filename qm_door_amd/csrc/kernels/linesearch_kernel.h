@@ -6,6 +6,7 @@
 // evaluating the node terms assembled in qm_interface/src/QMInterface.cpp:99-131.
 #pragma once
 #include "layout.h"
+#include "ls_lds.h"
 #include "schedule_dev.h"
 #include "sweep_dev.h"
 
@@ -30,20 +31,19 @@ struct LsArgs {
   int* done;       // [batch] convergence flags (see InitArgs)
 };
 
-// dynamic LDS of a line-search launch that keeps the trial trajectories on chip: 0 if they do not fit beside the static arrays
-constexpr int LS_STATIC_LDS_BYTES = (3 * 256 + 8 + 1800) * int(sizeof(real)) + int(sizeof(ModelR)) + 256 * 4 + 256;
-inline int lsTrialLdsBytes(int N, int threads = 256) {
-  const int trials = (N + 1 <= threads / 2) ? 2 : 1;
-  const long long need = (long long)trials * (2 * N + 1) * 30 * (long long)sizeof(real);
-  return need + LS_STATIC_LDS_BYTES <= 160 * 1024 ? int(need) : 0;
-}
 // Threads per workgroup of a line-search launch.  256 = two trial steps side by side (the kernel comment): right while every instance has a CU of its own, where
 // the launch lasts as long as its slowest instance.  With more instances than CUs the launch is a queue, throughput counts, and the speculative second trial (wasted
 // in every instance that accepts the full step: all of them in the bench sets) is better spent on a second INSTANCE: 128 threads evaluate one trial at a time with
 // the same node-to-thread assignment and the same order of summation (64 < N + 1 <= 128: half = 128 either way; N + 1 <= 64: one node per thread either way --
 // merit, violation, alpha, step type and the iterate are bit-identical),
 // one trial's trajectories in LDS (48 KB at N = 100 instead of 96), so two workgroups share a CU.
-inline int lsThreads(int B, int N, int cus) { return (B > cus && N + 1 <= 128) ? 128 : 256; }
+inline int lsThreads(int B, int N, int cus) { return (B > cus && N + 1 <= LS_MAX_THREADS / 2) ? LS_MAX_THREADS / 2 : LS_MAX_THREADS; }
+// the launch shape of one call: threads per workgroup, dynamic LDS (ls_lds.h: lsTrialLdsBytes) and the LsArgs::trialInLds that has to go with it
+struct LsLaunch { int threads, dynamicLdsBytes, trialInLds; };
+inline LsLaunch lsLaunch(int B, int N, int cus) {
+  const int threads = lsThreads(B, N, cus), bytes = lsTrialLdsBytes(N, threads);
+  return LsLaunch{threads, bytes, bytes > 0};
+}
 
 struct DblIn {
   const real* x; const real* u; real dtS; const real* k1;
@@ -228,17 +228,17 @@ __device__ __forceinline__ real sumSquaresStrided(const real* v, int n, int firs
 // the called node evaluation saves and restores 156 callee-saved registers per lane through scratch memory -- 1,248 B per lane, 0.16 GB of HBM traffic per step and
 // 14 % of this kernel's time (profiles/r04h_variant_timing.txt: 0.109 -> 0.095 ms).  The profiling build keeps one translation unit (its clocks live in one device symbol).
 #if defined(QM_LS_EXTERN) && !defined(QM_RICCATI_TIMING)
-__global__ void __launch_bounds__(256) linesearch_kernel(LsArgs a);
+__global__ void __launch_bounds__(LS_MAX_THREADS) linesearch_kernel(LsArgs a);
 #else
-__global__ void __launch_bounds__(256) linesearch_kernel(LsArgs a) {
+__global__ void __launch_bounds__(LS_MAX_THREADS) linesearch_kernel(LsArgs a) {
 #ifdef QM_RICCATI_TIMING
   unsigned long long lsClk = clock64();
 #endif
-  __shared__ real red[3 * 256];
-  __shared__ real ctl[8];
-  __shared__ int structVotes[256];   // per thread: one of my weight entries lies outside the structured pattern
-  __shared__ ModelR mdS;   // the model constants: the sweeps read them with wave-uniform indices, from LDS instead of through the scalar cache
-  __shared__ __attribute__((aligned(16))) real wQ[900], wR[900];   // state / input weights of the tracking cost: every lane reads all 1800 of them per node
+  // the fixed part of the workgroup's LDS (ls_lds.h says what each array is for, and why they are six objects and not one)
+  __shared__ LsRed red; __shared__ LsCtlWords ctl; __shared__ LsVotes structVotes; __shared__ ModelR mdS;
+  __shared__ __attribute__((aligned(16))) LsWeights wQ, wR;
+  static_assert(lsLdsBytes(sizeof(red)) + lsLdsBytes(sizeof(ctl)) + lsLdsBytes(sizeof(structVotes)) + lsLdsBytes(sizeof(mdS)) + lsLdsBytes(sizeof(wQ)) + lsLdsBytes(sizeof(wR)) == LS_STATIC_LDS_BYTES,
+                "a __shared__ array added here goes into this sum and into LS_STATIC_LDS_BYTES by hand: compare both with .group_segment_fixed_size in the assembly");
   const int inst = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
   if (a.done[inst]) return;   // converged in an earlier iteration of this call: outputs and statistics stay as they are
   const int N = a.N;
@@ -258,15 +258,15 @@ __global__ void __launch_bounds__(256) linesearch_kernel(LsArgs a) {
   // trial trajectories: in LDS when the launch reserved room for them (every lane then reads its node's x, u, x_next from LDS instead of
   // 90 scattered HBM loads per node); in the HBM scratch otherwise (long horizons)
   QM_DYNAMIC_LDS(trialLds);
-  real* Xt = a.trialInLds ? trialLds + size_t(myTr) * (2 * N + 1) * 30 : a.Xt + (size_t(inst) * 2 + myTr) * (N + 1) * 30;
-  real* Ut = a.trialInLds ? Xt + (N + 1) * 30 : a.Ut + (size_t(inst) * 2 + myTr) * N * 30;
+  real* Xt = a.trialInLds ? trialLds + size_t(myTr) * lsTrialRows(N) * NX : a.Xt + (size_t(inst) * 2 + myTr) * (N + 1) * 30;
+  real* Ut = a.trialInLds ? Xt + (N + 1) * NX : a.Ut + (size_t(inst) * 2 + myTr) * N * 30;
 
   // the weights into LDS; while copying, every thread checks its entries against the structured pattern (nodePerformance: weightStructure) and records a vote
-  // (structVotes[tid] = 1: an entry outside the pattern); thread 0 combines the votes below, after the barrier, into ctl[7] = 1 (structured) / 0 (dense forms)
+  // (structVotes[tid] = 1: an entry outside the pattern); thread 0 combines the votes below, after the barrier, into ctl[LS_STRUCTURED] = 1 (structured) / 0 (dense forms)
   // the model constants and the baseline node metrics are requested together with the weights: ONE memory round trip for the prologue (were three in a row)
-  constexpr int MDW = (int(sizeof(ModelR) / 4) + 255) / 256;   // 32-bit words of the model per thread of a 256-thread launch
+  constexpr int MDW = (int(sizeof(ModelR) / 4) + LS_MAX_THREADS - 1) / LS_MAX_THREADS;   // 32-bit words of the model per thread of a full launch
   int mdw[2 * MDW];                                            // (a 128-thread launch takes twice as many)
-  const int mdPer = nthr >= 256 ? MDW : 2 * MDW;
+  const int mdPer = nthr >= LS_MAX_THREADS ? MDW : 2 * MDW;
   real m0 = 0.0_r, d0 = 0.0_r, e0 = 0.0_r;
   {
     bool outside = false;
@@ -313,20 +313,20 @@ __global__ void __launch_bounds__(256) linesearch_kernel(LsArgs a) {
   }
   // baseline performance (sum of the LQ kernel's node metrics): the first node of every thread came with the prologue's loads, the others (horizons beyond the thread count) here
   for (int k = tid + nthr; k <= N; k += nthr) { const real* m = a.metrics + (size_t(inst) * (N + 1) + k) * NODE_METRICS; m0 += m[0]; d0 += m[1]; e0 += m[2]; }
-  red[tid] = m0; red[256 + tid] = d0; red[512 + tid] = e0;
+  red[0][tid] = m0; red[1][tid] = d0; red[2][tid] = e0;
   __syncthreads();
   if (tid == 0) {
     real s0 = 0, s1 = 0, s2 = 0;
     int dense = 0;
     const int nSum = N + 1 < nthr ? N + 1 : nthr;   // threads beyond the last node hold exact zeros: the sum over the nodes, in node order, is the same number
-    for (int i = 0; i < nSum; ++i) { s0 += red[i]; s1 += red[256 + i]; s2 += red[512 + i]; }
+    for (int i = 0; i < nSum; ++i) { s0 += red[0][i]; s1 += red[1][i]; s2 += red[2][i]; }
     for (int i = 0; i < nthr; ++i) dense |= structVotes[i];
-    ctl[0] = s0; ctl[1] = sqrt(s1 + s2); ctl[7] = dense ? 0.0_r : 1.0_r;
+    ctl[LS_MERIT0] = s0; ctl[LS_VIOL0] = sqrt(s1 + s2); ctl[LS_STRUCTURED] = dense ? 0.0_r : 1.0_r;
   }
   __syncthreads();
   QM_LS_CLOCK(0);
-  const real merit0 = ctl[0], viol0 = ctl[1];
-  const int weightStructure = int(ctl[7]);
+  const real merit0 = ctl[LS_MERIT0], viol0 = ctl[LS_VIOL0];
+  const int weightStructure = int(ctl[LS_STRUCTURED]);
   const real armijo = a.instStats[size_t(inst) * 4 + 0];
   const real ricStatus = a.instStats[size_t(inst) * 4 + 1];
 
@@ -350,7 +350,7 @@ __global__ void __launch_bounds__(256) linesearch_kernel(LsArgs a) {
       cs += c; ds += d; es += e;
     }
     QM_LS_CLOCK(2);
-    red[tid] = cs; red[256 + tid] = ds; red[512 + tid] = es;
+    red[0][tid] = cs; red[1][tid] = ds; red[2][tid] = es;
     __syncthreads();
     QM_LS_CLOCK(3);
     if (tid == 0) {
@@ -360,7 +360,7 @@ __global__ void __launch_bounds__(256) linesearch_kernel(LsArgs a) {
         if (tr && al < st.alpha_min) break;        // the sequential loop would have stopped before this trial
         real s0 = 0, s1 = 0, s2 = 0;
         const int nTrial = N + 1 < half ? N + 1 : half;   // as above: the threads of the trial beyond its last node hold zeros
-        for (int i = tr * half; i < tr * half + nTrial; ++i) { s0 += red[i]; s1 += red[256 + i]; s2 += red[512 + i]; }
+        for (int i = tr * half; i < tr * half + nTrial; ++i) { s0 += red[0][i]; s1 += red[1][i]; s2 += red[2][i]; }
         m1 = s0; v1 = sqrt(s1 + s2);
         bool ok;
         // upstream FilterLinesearch::acceptStep
@@ -371,13 +371,13 @@ __global__ void __launch_bounds__(256) linesearch_kernel(LsArgs a) {
         accAlpha = al;
         if (ok) acc = 1.0_r;
       }
-      ctl[2] = m1; ctl[3] = v1; ctl[4] = acc; ctl[5] = real(type); ctl[6] = accAlpha;
+      ctl[LS_MERIT1] = m1; ctl[LS_VIOL1] = v1; ctl[LS_ACCEPTED] = acc; ctl[LS_STEP_TYPE] = real(type); ctl[LS_ALPHA] = accAlpha;
     }
     __syncthreads();
     QM_LS_CLOCK(4);
-    merit1 = ctl[2]; viol1 = ctl[3]; stepType = int(ctl[5]);
-    accepted = ctl[4] != 0.0_r;
-    const real lastAlpha = ctl[6];
+    merit1 = ctl[LS_MERIT1]; viol1 = ctl[LS_VIOL1]; stepType = int(ctl[LS_STEP_TYPE]);
+    accepted = ctl[LS_ACCEPTED] != 0.0_r;
+    const real lastAlpha = ctl[LS_ALPHA];
     __syncthreads();
     if (accepted) { alpha = lastAlpha; break; }
     alpha = lastAlpha * st.alpha_decay;
@@ -393,11 +393,11 @@ __global__ void __launch_bounds__(256) linesearch_kernel(LsArgs a) {
   // ---- upstream SqpSolver::checkConvergence: iteration limit, step size, metrics, primal step (l2 norms over the whole horizon)
   const real sx = sumSquaresStrided(dX, (N + 1) * 30, tid, nthr), su = sumSquaresStrided(dU, N * 30, tid, nthr);
   __syncthreads();
-  red[tid] = sx; red[256 + tid] = su;
+  red[0][tid] = sx; red[1][tid] = su;
   __syncthreads();
   if (tid == 0) {
     real s0 = 0, s1 = 0;
-    for (int i = 0; i < nthr; ++i) { s0 += red[i]; s1 += red[256 + i]; }
+    for (int i = 0; i < nthr; ++i) { s0 += red[0][i]; s1 += red[1][i]; }
     int conv = 0;
     if (a.iteration + 1 >= st.sqp_iterations) conv = 1;
     else if (alpha < st.alpha_min) conv = 2;

@@ -45,7 +45,7 @@ constexpr auto LV_COST = ldsAfter<real>(LV_Q, 30 + 2);         // cost: per-lane
 constexpr LqRegion LQ_VEC{LV_B.off, LV_COST.end() - LV_B.off};
 constexpr int LQ_LDS_DOUBLES = LQ_VEC.end();
 static_assert(LQ_LDS_DOUBLES == 1628 && LQ_VEC.count == 84 + 64 + 32 + 32, "the carve as it was measured: 13,024 B at fp64");
-static_assert(LQ_LDS_DOUBLES * sizeof(real) * 12 <= 160 * 1024, "twelve nodes per CU");
+static_assert(LQ_LDS_DOUBLES * sizeof(real) * 12 <= QM_CU_LDS_BYTES, "twelve nodes per CU");
 
 // ---- guests of X
 // x u x_next dx [4][XU_LD]: ticks 0..3, dead at the sync in front of the QR (tick 5).  fin[64], red[64] behind them: red in the terminal path (tick 1, beside

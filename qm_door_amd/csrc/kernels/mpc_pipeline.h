@@ -81,7 +81,7 @@ template <class Alloc> inline void ensureDdpBuffers(MpcBuffers& m, Alloc&& alloc
 
 inline hipError_t prepareMpcKernels() {
   const hipError_t e = QM_ALLOW_DYNAMIC_LDS(riccati_kernel<RICCATI_WAVES>, RICCATI_LDS_BYTES);
-  return e != hipSuccess ? e : QM_ALLOW_DYNAMIC_LDS(linesearch_kernel, 160 * 1024 - LS_STATIC_LDS_BYTES);
+  return e != hipSuccess ? e : QM_ALLOW_DYNAMIC_LDS(linesearch_kernel, QM_CU_LDS_BYTES - LS_STATIC_LDS_BYTES);
 }
 
 // Where the fp32 build stages the fp64 arrays of a call (one array per converted argument); the fp64 build passes the caller's arrays on and has none.
@@ -141,9 +141,10 @@ inline void enqueueMpcKernels(hipStream_t s, const MpcBuffers& m, const MpcIo& i
                 m.dTgrid, m.dDtgrid, m.dNodePhase, m.dX, m.dU, it, m.dDone};
     QM_LAUNCH(mpc_init_kernel, B, 128, s, ia);
     enqueueLqRiccati(s, m, io, debugLq ? m.dDebug : nullptr, ev);
+    const LsLaunch shape = lsLaunch(B, N, m.cus);
     LsArgs ls{m.dP, m.dRw, B, N, io.K, io.lineSearch, io.eeContact, m.dTgrid, m.dDtgrid, m.dNodePhase, m.dX, m.dU, m.ddX, m.ddU, io.targetTimes, io.targetStates, io.schedNum,
-              io.schedTimes, io.schedModes, m.dMetrics, m.dInstStats, m.dNodeMode, m.dXt, m.dUt, io.outT, io.outX, io.outU, io.outMode, io.outStats, it, lsTrialLdsBytes(N, lsThreads(B, N, m.cus)) > 0, m.dDone};
-    QM_LAUNCH_DYN(linesearch_kernel, B, lsThreads(B, N, m.cus), lsTrialLdsBytes(N, lsThreads(B, N, m.cus)), s, ls);
+              io.schedTimes, io.schedModes, m.dMetrics, m.dInstStats, m.dNodeMode, m.dXt, m.dUt, io.outT, io.outX, io.outU, io.outMode, io.outStats, it, shape.trialInLds, m.dDone};
+    QM_LAUNCH_DYN(linesearch_kernel, B, shape.threads, shape.dynamicLdsBytes, s, ls);
     recordTiming(ev, EV_LINE_SEARCH, s);
   }
 }

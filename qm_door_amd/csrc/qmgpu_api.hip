@@ -261,7 +261,7 @@ int qmgpu_debug_poison(qmgpu_handle h) {
   return onHandle(h, [&]() {
     joinWbc(h);      // (a pending WBC still reads the policy buffers, which are scratch)
     for (auto& sc : h->scratch) HIP_CHECK(hipMemsetAsync(sc.first, 0xFF, sc.second, h->stream));
-    constexpr int kDoubles = 160 * 1024 / 8;
+    constexpr int kDoubles = QM_CU_LDS_BYTES / 8;
     HIP_CHECK(QM_ALLOW_DYNAMIC_LDS(lds_poison_kernel, kDoubles * 8));
     QM_LAUNCH_DYN(lds_poison_kernel, 4096, 256, kDoubles * 8, h->stream, kDoubles, static_cast<double*>(nullptr));
     HIP_CHECK(hipGetLastError());

@@ -414,6 +414,43 @@ def check_lq_blocks_of_every_contact_mode(itf, oracle, solve):
                 assert np.abs(g[key] - o[key]).max() <= 1e-10 * max(1.0, np.abs(o[key]).max()), (mode, k, key)
 
 
+def rejected_full_step_batch(itf, oracle, N):
+    """Three instances whose line search does NOT accept the full step (every other scenario of the suite and every bench set does): the nominal stance held over the
+    whole horizon as the warm start -- a deliberately poor one -- against a target so far away (base 0.5 m and 0.5 rad, arm joints 0.3 rad, end-effector 0.6 m, times a
+    scale per instance) that the Newton step leaves the region where the linearised dynamics hold: its constraint violation exceeds the iterate's and the filter
+    halves the step, once for the second instance and at least twice for the third.  The scales per horizon were chosen with the oracle; the check below asserts what
+    they were chosen for.  Returns x0, tt, ts, nev, ev, md (one schedule for all), X, U."""
+    B, dt = 3, itf.problem.settings.dt
+    scales = {7: (0.5, 1.0, 4.0), 130: (1.0, 2.0, 8.0)}[N]
+    x0 = np.tile(itf.initial_state, (B, 1))
+    nev, ev, md = trot_schedule(N * dt + 1.0, phase0=0.03)
+    tt = np.zeros((B, 1)); ts = np.tile(nominal_target(oracle, itf.initial_state), (B, 1, 1)).copy()
+    for i, sc in enumerate(scales):
+        ts[i, 0, 6:9] += sc * np.array([0.5, 0.3, 0.05]); ts[i, 0, 9] += sc * 0.5; ts[i, 0, 24:30] += sc * 0.3; ts[i, 0, 30:33] += sc * np.array([0.5, 0.3, 0.2])
+    X = np.tile(itf.initial_state, (B, N + 1, 1))
+    U = np.tile(np.array([nominal_input(itf.robot_mass, oracle.node_mode_at(ev[:nev], md[:nev + 1], k * dt)) for k in range(N)]), (B, 1, 1))
+    return x0, tt, ts, nev, ev, md, X, U
+
+
+def check_rejected_full_step(itf, oracle, N, solve, tol):
+    """The line search's paths behind a rejected trial against the oracle: the second trial's slice of the trial trajectories, the hand-over of a rejected trial through
+    the control words, and the pass with a decayed alpha.  N = 7: two trials side by side, one node per thread; N = 130: one trial per pass, its slice in LDS.
+    solve(B, N, x0, tt, ts, nev, ev, md, X, U) runs one warm-started MPC call and returns dict(X, U, mode, stats); tol: the tier's bound on X and U (rel-inf).
+    The comparison is the whole-batch one (parity_report / assert_parity: X, U, modes, alpha, step type) plus merit and violation before and after the step."""
+    x0, tt, ts, nev, ev, md, X, U = batch = rejected_full_step_batch(itf, oracle, N)
+    B = x0.shape[0]
+    each = [oracle.mpc_solve(N, 0.0, x0[i], tt[i], ts[i], nev, ev, md, warm=(X[i], U[i])) for i in range(B)]
+    ref = {k: np.stack([r[k] for r in each]) for k in ("X", "U", "mode", "stats")}
+    alphas = ref["stats"][:, 4]
+    assert alphas[0] == 1.0 and alphas[1] == 0.5 and 0.0 < alphas[2] <= 0.25, alphas   # (<= 0.25: a second pass of the trial loop)
+    got = solve(B, N, x0, tt, ts, np.full(B, nev, dtype=np.int32), np.tile(ev, (B, 1)), np.tile(md, (B, 1)), X, U)
+    rep = parity_report(f"rejected_full_step_N{N}", got, ref, tau=False, record=False)
+    print(f"N={N}: alpha {got['stats'][:, 4]} / {alphas}, merit1 viol1 {got['stats'][:, 2:4].tolist()} / {ref['stats'][:, 2:4].tolist()}, X {rep['X']['max']:.2e}, U {rep['U']['max']:.2e}")
+    assert_parity(rep, tol=tol)
+    assert np.allclose(got["stats"][:, :4], ref["stats"][:, :4], rtol=1e-8, atol=1e-10), (got["stats"][:, :4], ref["stats"][:, :4])
+    return got, batch
+
+
 def nominal_target(oracle, x_nom):
     _, _, ee, eq, _ = oracle.kinematics(x_nom, np.zeros(30))
     return np.r_[x_nom, ee, eq]

@@ -86,6 +86,34 @@ def test_emu_line_search_launch_shape_for_batches_beyond_the_cus(emu):
     assert np.isfinite(res["2"][0]).all() and (res["2"][2][:, 4] > 0).all()   # a step was taken in every instance
 
 
+def _emu_warm_solve(itf, cus=None):
+    def solve(B, N, x0, tt, ts, nev, ev, md, X, U):
+        if cus is None:
+            sol = api.GpuSolver(itf, max_batch=B, max_nodes=N)
+        else:
+            os.environ["QMGPU_EMU_CUS"] = cus
+            try:
+                sol = api.GpuSolver(itf, max_batch=B, max_nodes=N)
+            finally:
+                del os.environ["QMGPU_EMU_CUS"]
+        oT, oX, oU, oM, oS = np.zeros((B, N + 1)), np.zeros((B, N + 1, 30)), np.zeros((B, N, 30)), np.zeros((B, N + 1), dtype=np.int32), np.zeros((B, abi.NSTATS))
+        sol.mpc(sol.mpc_args(B, N, x0, tt, ts, nev, ev.copy(), md.copy(), oT, oX, oU, oM, oS, t0=np.zeros(B), warm_x=X, warm_u=U))
+        return dict(X=oX, U=oU, mode=oM, stats=oS)
+    return solve
+
+
+@pytest.mark.parametrize("N", [7, 130])
+def test_emu_line_search_behind_a_rejected_full_step(emu, N):
+    """support.check_rejected_full_step on the emulated kernels (tests/test_gpu_edges.py has the GPU twin); at N = 7 also in the 128-thread launch shape
+    (QMGPU_EMU_CUS = 2 < B, as the test above): bit for bit the 256-thread result."""
+    itf, orc = emu
+    got, (x0, tt, ts, nev, ev, md, X, U) = S.check_rejected_full_step(itf, orc, N, _emu_warm_solve(itf), tol=1e-8)
+    if N == 7:
+        B = x0.shape[0]
+        narrow = _emu_warm_solve(itf, cus="2")(B, N, x0, tt, ts, np.full(B, nev, dtype=np.int32), np.tile(ev, (B, 1)), np.tile(md, (B, 1)), X, U)
+        assert all(np.array_equal(got[k], narrow[k]) for k in ("X", "U", "mode", "stats"))
+
+
 def test_emu_wbc(emu):
     itf, orc = emu
     rng = np.random.default_rng(3)

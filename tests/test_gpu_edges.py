@@ -164,6 +164,42 @@ def test_horizon_beyond_the_line_search_lds_budget(interface, oracle):
     assert np.abs(r32["U"] - r["U"]).max() <= 1e-4 * max(1.0, np.abs(r["U"]).max())
 
 
+@pytest.mark.parametrize("N", [7, 130])
+def test_line_search_behind_a_rejected_full_step(interface, oracle, N):
+    """support.check_rejected_full_step on the device: accepted step lengths 1, 1/2 and <= 1/4 in one batch, two trials side by side (N = 7) and one trial per pass
+    with its slice in LDS (N = 130)."""
+    import gpu_harness as G
+
+    def solve(B, N, x0, tt, ts, nev, ev, md, X, U):
+        sol = G.make_solver(interface, B, N)
+        mb = G.MpcBatch(x0, tt, ts, nev, ev, md, N, warm=(X, U))
+        sol.mpc(mb.args)
+        return mb.results()
+    S.check_rejected_full_step(interface, oracle, N, solve, tol=1e-6)
+
+
+def test_longest_horizons_whose_trial_slice_stays_in_lds(interface, oracle):
+    """The line search keeps one trial's trajectories in dynamic LDS while they fit beside its fixed arrays (ls_lds.h: lsTrialLdsBytes): up to N = 289 at fp64
+    (24,496 + 579 x 30 x 8 = 163,456 B of the CU's 163,840) and N = 628 at fp32 (12,848 + 1,257 x 30 x 4 = 163,688 B).  Both launches sit within 400 B of the
+    budget; one node more and the slice goes through the HBM scratch (test_horizon_beyond_the_line_search_lds_budget).  fp64 against the oracle, fp32 against fp64."""
+    import gpu_harness as G
+    mb, (x0, tt, ts, nev, ev, md) = _batch(G, interface, oracle, 1, 289, seed=8)
+    G.make_solver(interface, 1, 289).mpc(mb.args)
+    r = mb.results()
+    ref = oracle.mpc_solve(289, 0.0, x0[0], tt[0], ts[0], nev, ev, md)
+    assert r["stats"][0][7] == 0 and np.array_equal(r["mode"][0], ref["mode"]) and r["stats"][0][4] == ref["stats"][4]
+    assert np.abs(r["X"][0] - ref["X"]).max() <= 1e-6 * max(1.0, np.abs(ref["X"]).max())
+    assert np.abs(r["U"][0] - ref["U"]).max() <= 1e-6 * max(1.0, np.abs(ref["U"]).max())
+    res = {}
+    for dtype in ("f64", "f32"):
+        mb, _ = _batch(G, interface, oracle, 1, 628, seed=8)
+        G.make_solver(interface, 1, 628, dtype=dtype).mpc(mb.args)
+        res[dtype] = mb.results()
+    assert np.array_equal(res["f32"]["mode"], res["f64"]["mode"]) and (res["f32"]["stats"][:, 4] == res["f64"]["stats"][:, 4]).all() and (res["f32"]["stats"][:, 7] == 0).all()
+    assert np.abs(res["f32"]["X"] - res["f64"]["X"]).max() <= 1e-4 * max(1.0, np.abs(res["f64"]["X"]).max())
+    assert np.abs(res["f32"]["U"] - res["f64"]["U"]).max() <= 1e-4 * max(1.0, np.abs(res["f64"]["U"]).max())
+
+
 def test_barrier_constants_follow_a_settings_update(interface, oracle):
     """The relaxed-barrier constants that input_weight_kernel derives once per settings update (log delta, value(-lower) + value(upper) per arm joint; layout.h:
     QM_RW_DERIVED) must be re-derived by qmgpu_update_settings: the next MPC solve is the oracle's solve WITH the new barrier parameters, and differs from the old."""

@@ -196,7 +196,7 @@ int qmgpu_synchronize(qmgpu_handle h);
  * are complete after qmgpu_synchronize, or on the handle's stream after qmgpu_join_wbc (a device-side wait, no host wait) -- NOT after the caller synchronises its own stream.
  * Which calls join by themselves: qmgpu_cycle_batch (before its policy evaluation), qmgpu_wbc_solve_batch, qmgpu_set_stream (the NEW stream waits), qmgpu_set_overlap,
  * qmgpu_update_settings, qmgpu_debug_poison, qmgpu_synchronize, qmgpu_destroy.  Which do NOT: qmgpu_mpc_solve_batch, qmgpu_policy_eval_batch, qmgpu_mpc_feedback_batch, qmgpu_policy_eval_feedback_batch,
- * qmgpu_frontend_batch, qmgpu_warm_start_batch, qmgpu_gait_schedule_batch, qmgpu_get_input_weight, qmgpu_pack_results -- they touch nothing the library owns that a pending WBC reads or writes, and run next to it.
+ * qmgpu_mpc_value_function_batch, qmgpu_value_function_eval_batch, qmgpu_frontend_batch, qmgpu_warm_start_batch, qmgpu_gait_schedule_batch, qmgpu_get_input_weight, qmgpu_pack_results -- they touch nothing the library owns that a pending WBC reads or writes, and run next to it.
  * The pending WBC still READS the caller's rbd_measured / period / time (and ee_force) of that cycle and reads and writes input_last / working_set: those buffers must not
  * be modified -- by the caller's own kernels or copies on any stream, or through a non-joining call above -- until qmgpu_join_wbc, qmgpu_synchronize, or the next
  * qmgpu_cycle_batch / qmgpu_wbc_solve_batch has been issued on the handle. */
@@ -283,6 +283,29 @@ int qmgpu_mpc_feedback_batch(qmgpu_handle h, int batch, int num_nodes, const dou
 int qmgpu_policy_eval_feedback_batch(qmgpu_handle h, int batch, int num_nodes, const double* t_grid, const double* X, const double* uff /*[batch][N+1][30]*/,
                                      const double* K /*[batch][N+1][30][30]*/, const int32_t* modes, const double* t_eval, const double* x_measured /*[batch][30]*/,
                                      double* x_out /*[batch][30]*/, double* u_out /*[batch][30]*/, int32_t* mode_out /*[batch]*/);
+
+/* The SQP value function.  Replaces SqpSolver::extractValueFunction (sqp.createValueFunction): hpipm getRiccatiCostToGo, re-centred on the linearisation state.
+ * For k = 0 .. N, V_k(dx) is the optimal cost of the equality-constrained QP over nodes k .. N of the last SQP iteration the instance performed, as a function of
+ * its initial deviation dx_k = dx from the state the instance was linearised at:
+ *     Sm_k      Hessian of V_k (row-major, symmetric bit for bit),         sv_lin_k   gradient of V_k at dx = 0,
+ *     x_lin_k   the linearisation state (the warm start with row 0 = x0, or x0 at every node for a cold start),
+ *     Sv_k = sv_lin_k - Sm_k x_lin_k    (the form upstream stores, so that dfdx(x) = Sv_k + Sm_k x);       Sm_N = sym(Q_N), sv_lin_N = q_N.
+ * The constant term is not returned (upstream sets f = 0).  Whether to call is the host's decision: sqp.createValueFunction is not a field of the settings.
+ * Valid after a qmgpu_mpc_solve_batch / qmgpu_cycle_batch with QMGPU_ALG_SQP on the same QMGPU_F64 handle with the same batch and num_nodes; anything else
+ * (no solve yet, another shape, a QMGPU_ALG_DDP solve, a QMGPU_F32 handle) returns QMGPU_ERR_INVALID_ARGUMENT.  With sqp.sqpIteration > 1 the outputs of an
+ * instance belong to the last iteration it performed.  An instance whose solve was flagged (out_stats[7] != 0) gets Sm = 0, Sv = 0, sv_lin = 0, its x_lin, and
+ * status[i] != 0; status[i] = 0 otherwise.  All device pointers.  Enqueued on the handle's stream, no host synchronisation; reads only what the library owns and
+ * leaves every later solve bit-identical.  Does not join a WBC pending on the overlap stream. */
+int qmgpu_mpc_value_function_batch(qmgpu_handle h, int batch, int num_nodes, double* Sm /*[batch][N+1][30][30]*/, double* Sv /*[batch][N+1][30]*/,
+                                   double* sv_lin /*[batch][N+1][30] or NULL*/, double* x_lin /*[batch][N+1][30] or NULL*/, int32_t* status /*[batch] or NULL*/);
+
+/* Replaces SqpSolver::getValueFunction(time, state): Sm and Sv are interpolated linearly at t_eval exactly like U in qmgpu_policy_eval_batch (same interval, same
+ * weight, end values held), then
+ *     dfdxx = Sm(t),      dfdx = Sv(t) + Sm(t) x          (dfdxx symmetric bit for bit; f = 0 upstream, not returned).
+ * All device pointers; t_grid: out_t of the solve; Sm, Sv: the outputs of qmgpu_mpc_value_function_batch. */
+int qmgpu_value_function_eval_batch(qmgpu_handle h, int batch, int num_nodes, const double* t_grid, const double* Sm /*[batch][N+1][30][30]*/,
+                                    const double* Sv /*[batch][N+1][30]*/, const double* t_eval /*[batch]*/, const double* x /*[batch][30]*/,
+                                    double* dfdx /*[batch][30]*/, double* dfdxx /*[batch][30][30]*/);
 
 /* Initial guess of the next MPC call from the previous solution: (X, U) of the previous grid resampled (linear interpolation, end values held, as
  * upstream's LinearInterpolation) on new_grid [batch][new_nodes + 1]; x[0] of each instance is overwritten with x0 when x0 != NULL.  The results

@@ -217,6 +217,17 @@ class GpuSolver:
         abi.check(self.lib, self.lib.qmgpu_policy_eval_feedback_batch(self.handle, batch, num_nodes, _ptr(t_grid), _ptr(X), _ptr(uff), _ptr(K), _ptr(modes), _ptr(t_eval),
                                                                      _ptr(x_measured), _ptr(x_out), _ptr(u_out), _ptr(mode_out)))
 
+    def mpc_value_function(self, batch, num_nodes, Sm, Sv, sv_lin=None, x_lin=None, status=None):
+        """The SQP value function of the last mpc() / cycle() on this solver (qmgpu_mpc_value_function_batch; upstream's SqpSolver::extractValueFunction): per node the
+        Hessian Sm [batch][N+1][30][30] of the cost-to-go of the last QP and Sv [batch][N+1][30] with dfdx(x) = Sv_k + Sm_k x; optional sv_lin (the gradient at the
+        linearisation state), x_lin (that state), status [batch] int32 != 0 where the solve was flagged (zeros there)"""
+        abi.check(self.lib, self.lib.qmgpu_mpc_value_function_batch(self.handle, batch, num_nodes, _ptr(Sm), _ptr(Sv), _ptr(sv_lin), _ptr(x_lin), _ptr(status)))
+
+    def value_function_eval(self, batch, num_nodes, t_grid, Sm, Sv, t_eval, x, dfdx, dfdxx):
+        """dfdxx = Sm(t), dfdx = Sv(t) + Sm(t) x at t_eval [batch] for the states x [batch][30] (qmgpu_value_function_eval_batch; SqpSolver::getValueFunction)"""
+        abi.check(self.lib, self.lib.qmgpu_value_function_eval_batch(self.handle, batch, num_nodes, _ptr(t_grid), _ptr(Sm), _ptr(Sv), _ptr(t_eval), _ptr(x), _ptr(dfdx),
+                                                                    _ptr(dfdxx)))
+
     def pack_results(self, batch, num_nodes, X, U, wbc_out, modes, packed):
         """X | U | WBC output | modes of every instance into one row of `packed` [batch][sharding.pack_len(N)] on the handle's stream (qmgpu_pack_results): the all-gather record"""
         abi.check(self.lib, self.lib.qmgpu_pack_results(self.handle, batch, num_nodes, _ptr(X), _ptr(U), _ptr(wbc_out), _ptr(modes), _ptr(packed)))

@@ -18,6 +18,7 @@
 #include "host/host_error.h"
 #include "kernels/mpc_pipeline.h"
 #include "kernels/feedback_kernel.h"
+#include "kernels/value_kernel.h"
 #include "kernels/wbc_kernel.h"
 #include "kernels/frontend_kernel.h"
 #include "mpc32.h"
@@ -64,7 +65,7 @@ struct qmgpu_context {
   long callCount = 0;   // calls recorded since timing was enabled
   hipEvent_t* ev = ring[0];
   double lastMs[5] = {0, 0, 0, 0, 0};
-  int lastBatch = 0, lastN = 0, lastAlgorithm = QMGPU_ALG_SQP;   // shape and solver of the last solve: what qmgpu_mpc_feedback_batch / qmgpu_debug_get_lq may read
+  int lastBatch = 0, lastN = 0, lastAlgorithm = QMGPU_ALG_SQP;   // shape and solver of the last solve: what qmgpu_mpc_feedback_batch / qmgpu_mpc_value_function_batch / qmgpu_debug_get_lq may read
 
   std::vector<std::pair<void*, size_t>> scratch;   // buffers every call rewrites (qmgpu_debug_poison fills them with NaN)
   template <class T> T* alloc(size_t count, bool isScratch = true) {
@@ -142,6 +143,7 @@ int qmgpu_create_ex(const qmgpu_problem* problem, int device, int max_batch, int
     for (auto& set : ctx->ring) for (auto& e : set) HIP_CHECK(hipEventCreate(&e));
     HIP_CHECK(QM_ALLOW_DYNAMIC_LDS(wbc_kernel, WBC_LDS_BYTES));
     HIP_CHECK(prepareMpcKernels());
+    HIP_CHECK(QM_ALLOW_DYNAMIC_LDS(value_function_kernel, VALUE_LDS_BYTES));
     QM_LAUNCH(input_weight_kernel, 1, 64, ctx->stream, ctx->m.dP, ctx->m.dZeros, ctx->m.dRw);
     HIP_CHECK(hipGetLastError());
     if (dtype == QMGPU_F32) ctx->m32 = qmk32::create(*problem, max_batch, max_nodes, ctx->stream, ctx->rawAlloc);
@@ -344,17 +346,44 @@ int qmgpu_policy_eval_batch(qmgpu_handle h, int batch, int num_nodes, const doub
   });
 }
 
+// what qmgpu_mpc_feedback_batch and qmgpu_mpc_value_function_batch read is the last solve's: an SQP solve of this shape on an fp64 handle
+static void checkLastSqpSolve(qmgpu_handle h, int batch, int num_nodes, const char* what) {
+  const std::string w(what);
+  if (h->dtype != QMGPU_F64) throw std::invalid_argument(w + " exists for QMGPU_F64 handles only");
+  if (h->lastBatch < 1) throw std::invalid_argument(w + " needs a solve on this handle first");
+  if (h->lastAlgorithm != QMGPU_ALG_SQP) throw std::invalid_argument(w + " exists for QMGPU_ALG_SQP solves only");
+  if (batch != h->lastBatch || num_nodes != h->lastN) throw std::invalid_argument("batch / num_nodes differ from the last solve on this handle");
+}
+
 int qmgpu_mpc_feedback_batch(qmgpu_handle h, int batch, int num_nodes, const double* X, const double* U, double* K, double* uff, int32_t* status) {
   if (!X || !U || !K || !uff || batch < 1 || num_nodes < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad feedback arguments");
   // reads the stage records, the Riccati gains and the sweep's status of the last solve (nothing a WBC pending on the overlap stream touches) plus X, U
   return onHandle(h, [&]() {
-    if (h->dtype != QMGPU_F64) throw std::invalid_argument("the feedback policy exists for QMGPU_F64 handles only");
-    if (h->lastBatch < 1) throw std::invalid_argument("qmgpu_mpc_feedback_batch needs a solve on this handle first");
-    if (h->lastAlgorithm != QMGPU_ALG_SQP) throw std::invalid_argument("the feedback policy exists for QMGPU_ALG_SQP solves only");
-    if (batch != h->lastBatch || num_nodes != h->lastN) throw std::invalid_argument("batch / num_nodes differ from the last solve on this handle");
+    checkLastSqpSolve(h, batch, num_nodes, "the feedback policy");
     static_assert(sizeof(int) == sizeof(int32_t), "status words");
     FeedbackArgs fa{batch, num_nodes, h->m.dStages, h->m.dGains, h->m.dInstStats, X, U, K, uff, status};
     QM_LAUNCH(feedback_gain_kernel, batch * (num_nodes + 1), 64, h->stream, fa);
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
+int qmgpu_mpc_value_function_batch(qmgpu_handle h, int batch, int num_nodes, double* Sm, double* Sv, double* sv_lin, double* x_lin, int32_t* status) {
+  if (!Sm || !Sv || batch < 1 || num_nodes < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad value-function arguments");
+  // reads the stage records, the Riccati gains, the step grid, the sweep's status and the iterate of the last solve: nothing a WBC pending on the overlap stream
+  // touches, nothing the line search writes (it reads dX and writes the caller's out_x)
+  return onHandle(h, [&]() {
+    checkLastSqpSolve(h, batch, num_nodes, "the value function");
+    ValueArgs va{batch, num_nodes, h->m.dStages, h->m.dGains, h->m.dDtgrid, h->m.dInstStats, h->m.dX, Sm, Sv, sv_lin, x_lin, status};
+    QM_LAUNCH_DYN(value_function_kernel, batch, VALUE_THREADS, VALUE_LDS_BYTES, h->stream, va);
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
+int qmgpu_value_function_eval_batch(qmgpu_handle h, int batch, int num_nodes, const double* t_grid, const double* Sm, const double* Sv, const double* t_eval, const double* x,
+                                    double* dfdx, double* dfdxx) {
+  if (!t_grid || !Sm || !Sv || !t_eval || !x || !dfdx || !dfdxx || batch < 1 || num_nodes < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad arguments");
+  return onHandle(h, [&]() {
+    QM_LAUNCH(value_eval_kernel, batch, 64, h->stream, batch, num_nodes, t_grid, Sm, Sv, t_eval, x, dfdx, dfdxx);
     HIP_CHECK(hipGetLastError());
   });
 }

@@ -196,7 +196,7 @@ int qmgpu_synchronize(qmgpu_handle h);
  * are complete after qmgpu_synchronize, or on the handle's stream after qmgpu_join_wbc (a device-side wait, no host wait) -- NOT after the caller synchronises its own stream.
  * Which calls join by themselves: qmgpu_cycle_batch (before its policy evaluation), qmgpu_wbc_solve_batch, qmgpu_set_stream (the NEW stream waits), qmgpu_set_overlap,
  * qmgpu_update_settings, qmgpu_debug_poison, qmgpu_synchronize, qmgpu_destroy.  Which do NOT: qmgpu_mpc_solve_batch, qmgpu_policy_eval_batch, qmgpu_mpc_feedback_batch, qmgpu_policy_eval_feedback_batch,
- * qmgpu_mpc_value_function_batch, qmgpu_value_function_eval_batch, qmgpu_frontend_batch, qmgpu_warm_start_batch, qmgpu_gait_schedule_batch, qmgpu_get_input_weight, qmgpu_pack_results -- they touch nothing the library owns that a pending WBC reads or writes, and run next to it.
+ * qmgpu_mpc_value_function_batch, qmgpu_value_function_eval_batch, qmgpu_mpc_dual_batch, qmgpu_frontend_batch, qmgpu_warm_start_batch, qmgpu_gait_schedule_batch, qmgpu_get_input_weight, qmgpu_pack_results -- they touch nothing the library owns that a pending WBC reads or writes, and run next to it.
  * The pending WBC still READS the caller's rbd_measured / period / time (and ee_force) of that cycle and reads and writes input_last / working_set: those buffers must not
  * be modified -- by the caller's own kernels or copies on any stream, or through a non-joining call above -- until qmgpu_join_wbc, qmgpu_synchronize, or the next
  * qmgpu_cycle_batch / qmgpu_wbc_solve_batch has been issued on the handle. */
@@ -306,6 +306,26 @@ int qmgpu_mpc_value_function_batch(qmgpu_handle h, int batch, int num_nodes, dou
 int qmgpu_value_function_eval_batch(qmgpu_handle h, int batch, int num_nodes, const double* t_grid, const double* Sm /*[batch][N+1][30][30]*/,
                                     const double* Sv /*[batch][N+1][30]*/, const double* t_eval /*[batch]*/, const double* x /*[batch][30]*/,
                                     double* dfdx /*[batch][30]*/, double* dfdxx /*[batch][30][30]*/);
+
+/* The SQP dual solution: what upstream's SqpSolver would hand to getStateInputEqualityConstraintLagrangian / getIntermediateDualSolution.  The multipliers of the
+ * equality-constrained QP of the last SQP iteration the instance performed, at its full step (dx, du) (alpha = 1), with the symmetric parts of Q, R:
+ *     lambda_N = Q_N dx_N + q_N
+ *     lambda_k = Q_k dx_k + q_k + A_k' lambda_{k+1} + C_k' nu_k          k = N-1 .. 0
+ *     0        = R_k du_k + r_k + B_k' lambda_{k+1} + D_k' nu_k          k = 0 .. N-1
+ *     costate   lambda_k (30 per node): the costate, the gradient of the cost-to-go at the step -- lambda_k = Sm_k dx_k + sv_lin_k of
+ *               qmgpu_mpc_value_function_batch, lambda_0 = sv_lin_0 (dx_0 = 0); the multiplier of the dynamics row that ends in node k (of dx_0 = 0 for k = 0),
+ *     nu        nu_k: the nc_k <= 16 multipliers of C_k dx + D_k du + e_k = 0 in the row order of qmgpu_debug_get_lq, rows >= nc_k written as zero
+ *               (D_k has full row rank: nu_k is unique),
+ *     nc        nc_k.
+ * Valid after a qmgpu_mpc_solve_batch / qmgpu_cycle_batch with QMGPU_ALG_SQP on the same QMGPU_F64 handle with the same batch and num_nodes; anything else
+ * (no solve yet, another shape, a QMGPU_ALG_DDP solve, a QMGPU_F32 handle) returns QMGPU_ERR_INVALID_ARGUMENT.  The costates need only what every solve leaves
+ * on the device.  nu also needs the un-projected blocks: a non-NULL nu is valid only if qmgpu_enable_debug(h, 1) was in force during that solve, and returns
+ * QMGPU_ERR_INVALID_ARGUMENT otherwise (costate, nc and status alone still work).  With sqp.sqpIteration > 1 the outputs of an instance belong to the last
+ * iteration it performed.  An instance whose solve was flagged (out_stats[7] != 0) gets costate = 0, nu = 0, its nc, and status[i] != 0; status[i] = 0 otherwise.
+ * All device pointers.  Enqueued on the handle's stream, no host synchronisation; reads only what the library owns and leaves every later solve bit-identical.
+ * Does not join a WBC pending on the overlap stream. */
+int qmgpu_mpc_dual_batch(qmgpu_handle h, int batch, int num_nodes, double* costate /*[batch][N+1][30]*/, double* nu /*[batch][N][16] or NULL*/,
+                         int32_t* nc /*[batch][N] or NULL*/, int32_t* status /*[batch] or NULL*/);
 
 /* Initial guess of the next MPC call from the previous solution: (X, U) of the previous grid resampled (linear interpolation, end values held, as
  * upstream's LinearInterpolation) on new_grid [batch][new_nodes + 1]; x[0] of each instance is overwritten with x0 when x0 != NULL.  The results

@@ -228,6 +228,12 @@ class GpuSolver:
         abi.check(self.lib, self.lib.qmgpu_value_function_eval_batch(self.handle, batch, num_nodes, _ptr(t_grid), _ptr(Sm), _ptr(Sv), _ptr(t_eval), _ptr(x), _ptr(dfdx),
                                                                     _ptr(dfdxx)))
 
+    def dual(self, batch, num_nodes, costate, nu=None, nc=None, status=None):
+        """The SQP dual solution of the last mpc() / cycle() on this solver (qmgpu_mpc_dual_batch): costate [batch][N+1][30], the multipliers lambda_k of the dynamics
+        rows; optional nu [batch][N][16], the multipliers of the state-input equality constraints in the row order of debug_lq (needs enable_debug() before the
+        solve; rows >= nc zero), nc [batch][N] int32, status [batch] int32 != 0 where the solve was flagged (zeros there)"""
+        abi.check(self.lib, self.lib.qmgpu_mpc_dual_batch(self.handle, batch, num_nodes, _ptr(costate), _ptr(nu), _ptr(nc), _ptr(status)))
+
     def pack_results(self, batch, num_nodes, X, U, wbc_out, modes, packed):
         """X | U | WBC output | modes of every instance into one row of `packed` [batch][sharding.pack_len(N)] on the handle's stream (qmgpu_pack_results): the all-gather record"""
         abi.check(self.lib, self.lib.qmgpu_pack_results(self.handle, batch, num_nodes, _ptr(X), _ptr(U), _ptr(wbc_out), _ptr(modes), _ptr(packed)))

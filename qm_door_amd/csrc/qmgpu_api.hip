@@ -19,6 +19,7 @@
 #include "kernels/mpc_pipeline.h"
 #include "kernels/feedback_kernel.h"
 #include "kernels/value_kernel.h"
+#include "kernels/dual_kernel.h"
 #include "kernels/wbc_kernel.h"
 #include "kernels/frontend_kernel.h"
 #include "mpc32.h"
@@ -66,6 +67,7 @@ struct qmgpu_context {
   hipEvent_t* ev = ring[0];
   double lastMs[5] = {0, 0, 0, 0, 0};
   int lastBatch = 0, lastN = 0, lastAlgorithm = QMGPU_ALG_SQP;   // shape and solver of the last solve: what qmgpu_mpc_feedback_batch / qmgpu_mpc_value_function_batch / qmgpu_debug_get_lq may read
+  bool lastDebugLq = false;                                      // whether that solve wrote the LQ dump (qmgpu_mpc_dual_batch reads it for nu)
 
   std::vector<std::pair<void*, size_t>> scratch;   // buffers every call rewrites (qmgpu_debug_poison fills them with NaN)
   template <class T> T* alloc(size_t count, bool isScratch = true) {
@@ -298,6 +300,7 @@ static void enqueueMpc(qmgpu_handle h, const qmgpu_mpc_args* a) {
     enqueueMpcSolve(h->stream, h->m, io, settings, h->debugLq, ev, h->rawAlloc);
   }
   h->lastBatch = a->batch; h->lastN = a->num_nodes; h->lastAlgorithm = a->algorithm;
+  h->lastDebugLq = h->dtype == QMGPU_F64 && a->algorithm == QMGPU_ALG_SQP && h->debugLq;
 }
 
 static void enqueueWbc(qmgpu_handle h, const qmgpu_wbc_args* w, hipStream_t stream) {
@@ -346,7 +349,7 @@ int qmgpu_policy_eval_batch(qmgpu_handle h, int batch, int num_nodes, const doub
   });
 }
 
-// what qmgpu_mpc_feedback_batch and qmgpu_mpc_value_function_batch read is the last solve's: an SQP solve of this shape on an fp64 handle
+// what qmgpu_mpc_feedback_batch, qmgpu_mpc_value_function_batch and qmgpu_mpc_dual_batch read is the last solve's: an SQP solve of this shape on an fp64 handle
 static void checkLastSqpSolve(qmgpu_handle h, int batch, int num_nodes, const char* what) {
   const std::string w(what);
   if (h->dtype != QMGPU_F64) throw std::invalid_argument(w + " exists for QMGPU_F64 handles only");
@@ -375,6 +378,21 @@ int qmgpu_mpc_value_function_batch(qmgpu_handle h, int batch, int num_nodes, dou
     checkLastSqpSolve(h, batch, num_nodes, "the value function");
     ValueArgs va{batch, num_nodes, h->m.dStages, h->m.dGains, h->m.dDtgrid, h->m.dInstStats, h->m.dX, Sm, Sv, sv_lin, x_lin, status};
     QM_LAUNCH_DYN(value_function_kernel, batch, VALUE_THREADS, VALUE_LDS_BYTES, h->stream, va);
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
+int qmgpu_mpc_dual_batch(qmgpu_handle h, int batch, int num_nodes, double* costate, double* nu, int32_t* nc, int32_t* status) {
+  if (!costate || batch < 1 || num_nodes < 1) return setError(QMGPU_ERR_INVALID_ARGUMENT, "bad dual-solution arguments");
+  // reads the stage records, the Riccati gains, the step grid, the sweep's status and the full step of the last solve, and for nu its LQ dump: nothing a WBC
+  // pending on the overlap stream touches, nothing a later solve reads before it has rewritten it
+  return onHandle(h, [&]() {
+    checkLastSqpSolve(h, batch, num_nodes, "the dual solution");
+    if (nu && !(h->lastDebugLq && h->m.dDebug)) throw std::invalid_argument("nu needs the LQ dump of the solve: call qmgpu_enable_debug(h, 1) before it");
+    static_assert(sizeof(int) == sizeof(int32_t), "nc and status words");
+    DualArgs da{batch, num_nodes, h->m.dStages, h->m.dGains, h->m.dDtgrid, h->m.dInstStats, h->m.ddX, h->m.ddU, nu ? h->m.dDebug : nullptr, h->m.dStageNc, costate, nu, nc, status};
+    QM_LAUNCH_DYN(costate_kernel, batch, DUAL_THREADS, DUAL_LDS_BYTES, h->stream, da);
+    if (nu || nc) QM_LAUNCH(dual_multiplier_kernel, batch * num_nodes, 64, h->stream, da);
     HIP_CHECK(hipGetLastError());
   });
 }

@@ -196,7 +196,7 @@ int qmgpu_synchronize(qmgpu_handle h);
  * are complete after qmgpu_synchronize, or on the handle's stream after qmgpu_join_wbc (a device-side wait, no host wait) -- NOT after the caller synchronises its own stream.
  * Which calls join by themselves: qmgpu_cycle_batch (before its policy evaluation), qmgpu_wbc_solve_batch, qmgpu_set_stream (the NEW stream waits), qmgpu_set_overlap,
  * qmgpu_update_settings, qmgpu_debug_poison, qmgpu_synchronize, qmgpu_destroy.  Which do NOT: qmgpu_mpc_solve_batch, qmgpu_policy_eval_batch, qmgpu_mpc_feedback_batch, qmgpu_policy_eval_feedback_batch,
- * qmgpu_mpc_value_function_batch, qmgpu_value_function_eval_batch, qmgpu_mpc_dual_batch, qmgpu_frontend_batch, qmgpu_warm_start_batch, qmgpu_gait_schedule_batch, qmgpu_get_input_weight, qmgpu_pack_results -- they touch nothing the library owns that a pending WBC reads or writes, and run next to it.
+ * qmgpu_mpc_value_function_batch, qmgpu_value_function_eval_batch, qmgpu_mpc_dual_batch, qmgpu_mpc_metrics_batch, qmgpu_frontend_batch, qmgpu_warm_start_batch, qmgpu_gait_schedule_batch, qmgpu_get_input_weight, qmgpu_pack_results -- they touch nothing the library owns that a pending WBC reads or writes, and run next to it.
  * The pending WBC still READS the caller's rbd_measured / period / time (and ee_force) of that cycle and reads and writes input_last / working_set: those buffers must not
  * be modified -- by the caller's own kernels or copies on any stream, or through a non-joining call above -- until qmgpu_join_wbc, qmgpu_synchronize, or the next
  * qmgpu_cycle_batch / qmgpu_wbc_solve_batch has been issued on the handle. */
@@ -327,6 +327,51 @@ int qmgpu_value_function_eval_batch(qmgpu_handle h, int batch, int num_nodes, co
 int qmgpu_mpc_dual_batch(qmgpu_handle h, int batch, int num_nodes, double* costate /*[batch][N+1][30]*/, double* nu /*[batch][N][16] or NULL*/,
                          int32_t* nc /*[batch][N] or NULL*/, int32_t* status /*[batch] or NULL*/);
 
+/* The SQP solution metrics: what upstream's SqpSolver::computePerformance forms after every iteration (multiple_shooting::computeIntermediateMetrics /
+ * computeTerminalMetrics per node, toPerformanceIndex over the horizon) and SolverBase::getSolutionMetrics / getPerformanceIndeces hand out.  The OCP -- costs, RK2
+ * defects, state-input equalities -- evaluated on ANY trajectory (time_grid, X, U): the outputs of a solve, a warm start, a perturbed iterate.
+ *     node_cost   Metrics::cost of the node, NOT dt-scaled; entry N the terminal cost.  Bit for bit the left-to-right sum of slots 0..6 of cost_terms.
+ *     cost_terms  [0] 1/2 dx'Q dx   [1] 1/2 du'R'du   [2] end-effector pose penalty (ee_mu_*, ee_final_mu_* at node N)   [3] arm joint-position relaxed barrier and
+ *                 [4] arm joint-velocity barrier, each with the constant offsets the line search subtracts   [5] friction-cone barrier over the stance feet
+ *                 [6] force tracking, exactly 0 with ee_contact_ref == NULL or ee_contact_stiffness == 0   [7] 0.   Terminal node: slot 2 only.
+ *     defect      rk2(x_k, u_k, dt_k) - x_{k+1}, dt_k = t_{k+1} - t_k  (Metrics::dynamicsViolation; the b of qmgpu_debug_get_lq at the same point)
+ *     eq          values of the state-input equalities in the row order of qmgpu_debug_get_lq's e, rows >= nc_k written as 0 (Metrics::stateInputEqConstraint)
+ *     nc          nc_k.  A node takes the contact mode that starts at its time, as the nodes of a solve do: nc equals the solve's for the same grid and schedule.
+ *     performance upstream's PerformanceIndex in its field order: [0] merit = cost (this SQP carries no Lagrangian terms)
+ *                 [1] cost = sum_{k<N} dt_k node_cost[k] + node_cost[N]   [2] dualFeasibilitiesSSE = 0
+ *                 [3] dynamicsViolationSSE = sum dt_k |defect_k|^2 (+ |x0 - X_0|^2 when x0 is given, as upstream counts the initial-state constraint)
+ *                 [4] equalityConstraintsSSE = sum dt_k |eq_k|^2   [5] inequalityConstraintsSSE = 0 (every inequality of this OCP is a soft-constraint cost)
+ *                 [6] equalityLagrangian = 0   [7] inequalityLagrangian = 0.
+ *                 The sums are formed in an order that depends on N only: an instance's eight numbers are the same bits alone and inside a larger batch.
+ *                 merit and sqrt([3] + [4]) without x0 are what out_stats[0..1] (at the iterate a solve starts from) and out_stats[2..3] (at out_x / out_u) hold,
+ *                 up to the order of summation.
+ * Stateless: needs no previous solve, reads the model, the settings and R' behind the handle plus these arrays, writes every entry of every non-NULL output and
+ * leaves every later solve bit-identical.  All device pointers.  Enqueued on the handle's stream, no host synchronisation.  QMGPU_F64 handles only; a QMGPU_F32
+ * handle, batch / num_nodes beyond the handle's capacity or a missing input return QMGPU_ERR_INVALID_ARGUMENT.  Does not join a WBC pending on the overlap stream.
+ * While timing is enabled the call is recorded like a solve; of its six durations only [5], the whole call, is filled. */
+enum { QMGPU_NCOST_TERMS = 8, QMGPU_NPERF = 8 };
+typedef struct qmgpu_metrics_args {
+  int32_t batch, num_nodes, num_target_knots, reserved;
+  const double* time_grid;             /* [batch][N+1]  (out_t of a solve, or any increasing grid) */
+  const double* X;                     /* [batch][N+1][30] */
+  const double* U;                     /* [batch][N][30] */
+  const double* x0;                    /* [batch][30] or NULL: adds |x0 - X_0|^2 to the dynamics SSE, as upstream does */
+  const double* target_times;          /* as qmgpu_mpc_args */
+  const double* target_states;
+  const int32_t* sched_num_events;
+  const double* sched_event_times;
+  const int32_t* sched_modes;
+  const double* ee_contact_ref;        /* as qmgpu_mpc_args, may be NULL */
+  /* outputs: device pointers, each may be NULL */
+  double* node_cost;                   /* [batch][N+1] */
+  double* cost_terms;                  /* [batch][N+1][QMGPU_NCOST_TERMS] */
+  double* defect;                      /* [batch][N][30] */
+  double* eq;                          /* [batch][N][16] */
+  int32_t* nc;                         /* [batch][N] */
+  double* performance;                 /* [batch][QMGPU_NPERF] */
+} qmgpu_metrics_args;
+int qmgpu_mpc_metrics_batch(qmgpu_handle h, const qmgpu_metrics_args* args);
+
 /* Initial guess of the next MPC call from the previous solution: (X, U) of the previous grid resampled (linear interpolation, end values held, as
  * upstream's LinearInterpolation) on new_grid [batch][new_nodes + 1]; x[0] of each instance is overwritten with x0 when x0 != NULL.  The results
  * are what qmgpu_mpc_args::warm_x / warm_u expect.  All device pointers; prev_* and warm_* must not alias. */
@@ -422,10 +467,12 @@ int qmgpu_debug_get_lq(qmgpu_handle h, int instance, int node, double* A, double
 /* Device time (ms) of each kernel of the last timed call, measured with HIP events on the handle's stream:
  * [0] ad_node  [1] lq_node (projection)  [2] riccati  [3] line search + update  [4] wbc  [5] whole call */
 int qmgpu_last_kernel_ms(qmgpu_handle h, double* ms6);
-/* Same, averaged over the last `last_calls` timed calls (event ring of 256 calls; no per-call host sync is needed). */
+/* Same, averaged over the last `last_calls` timed calls (event ring of 256 calls; no per-call host sync is needed).  Timed qmgpu_mpc_metrics_batch calls in that
+ * window are left out of the mean, so that the per-kernel times of the solves stay what they were; a window that holds nothing else returns their mean in [5]. */
 int qmgpu_kernel_ms_mean(qmgpu_handle h, int last_calls, double* ms6);
 /* The same six durations of EACH of the last `last_calls` timed calls, oldest first: ms6_per_call [last_calls][6] (a launch of the sequential kernels lasts as long as
- * its slowest instance: the spread from call to call is what a real-time caller has to budget for). */
+ * its slowest instance: the spread from call to call is what a real-time caller has to budget for).  A timed qmgpu_mpc_metrics_batch call is one of the calls:
+ * its row holds [5] only, [0..4] are 0. */
 int qmgpu_kernel_ms_history(qmgpu_handle h, int last_calls, double* ms6_per_call);
 int qmgpu_enable_timing(qmgpu_handle h, int enable);
 /* Test aid: fills every scratch buffer behind the handle and the LDS of every CU with NaN, so that a kernel reading memory that

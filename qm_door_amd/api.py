@@ -234,6 +234,27 @@ class GpuSolver:
         solve; rows >= nc zero), nc [batch][N] int32, status [batch] int32 != 0 where the solve was flagged (zeros there)"""
         abi.check(self.lib, self.lib.qmgpu_mpc_dual_batch(self.handle, batch, num_nodes, _ptr(costate), _ptr(nu), _ptr(nc), _ptr(status)))
 
+    @staticmethod
+    def metrics_args(batch, num_nodes, time_grid, X, U, target_times, target_states, sched_num, sched_times, sched_modes, x0=None, ee_contact_ref=None,
+                     node_cost=None, cost_terms=None, defect=None, eq=None, nc=None, performance=None):
+        """qmgpu_metrics_args: the trajectory (time_grid [batch][N+1], X, U), targets and schedule as mpc_args; x0 adds |x0 - X_0|^2 to the dynamics SSE; outputs, each
+        optional: node_cost [batch][N+1], cost_terms [batch][N+1][8], defect [batch][N][30], eq [batch][N][16], nc [batch][N] int32, performance [batch][8]"""
+        K = target_times.shape[-1] if target_times is not None and target_times.ndim > 1 else 1
+        a = abi.MetricsArgs()
+        a.batch, a.num_nodes, a.num_target_knots = batch, num_nodes, K
+        vals = (("time_grid", time_grid), ("X", X), ("U", U), ("x0", x0), ("target_times", target_times), ("target_states", target_states), ("sched_num_events", sched_num),
+                ("sched_event_times", sched_times), ("sched_modes", sched_modes), ("ee_contact_ref", ee_contact_ref), ("node_cost", node_cost), ("cost_terms", cost_terms),
+                ("defect", defect), ("eq", eq), ("nc", nc), ("performance", performance))
+        for name, val in vals:
+            setattr(a, name, _ptr(val))
+        a._keep = tuple(v for _, v in vals)
+        return a
+
+    def metrics(self, args):
+        """The SQP solution metrics (qmgpu_mpc_metrics_batch; upstream's SqpSolver::computePerformance / getSolutionMetrics): per-node cost and cost terms, RK2 defects,
+        values of the state-input equalities with nc, and the PerformanceIndex of the trajectory in `args` (metrics_args).  Stateless: needs no previous solve."""
+        abi.check(self.lib, self.lib.qmgpu_mpc_metrics_batch(self.handle, C.byref(args)))
+
     def pack_results(self, batch, num_nodes, X, U, wbc_out, modes, packed):
         """X | U | WBC output | modes of every instance into one row of `packed` [batch][sharding.pack_len(N)] on the handle's stream (qmgpu_pack_results): the all-gather record"""
         abi.check(self.lib, self.lib.qmgpu_pack_results(self.handle, batch, num_nodes, _ptr(X), _ptr(U), _ptr(wbc_out), _ptr(modes), _ptr(packed)))

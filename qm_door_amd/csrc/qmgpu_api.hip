@@ -20,6 +20,7 @@
 #include "kernels/feedback_kernel.h"
 #include "kernels/value_kernel.h"
 #include "kernels/dual_kernel.h"
+#include "kernels/metrics_kernel.h"
 #include "kernels/wbc_kernel.h"
 #include "kernels/frontend_kernel.h"
 #include "mpc32.h"
@@ -62,7 +63,7 @@ struct qmgpu_context {
   // HIP-event ring: one set of TIMING_EVENTS events (kernels/mpc_pipeline.h) per call while timing is enabled, read back without a per-call sync
   static constexpr int kRing = 256;
   hipEvent_t ring[kRing][TIMING_EVENTS] = {};
-  int ringKind[kRing];  // bit0: mpc recorded, bit1: wbc recorded
+  int ringKind[kRing];  // bit0: mpc recorded, bit1: wbc recorded, bit2: one launch between EV_START and EV_LINE_SEARCH (qmgpu_mpc_metrics_batch)
   long callCount = 0;   // calls recorded since timing was enabled
   hipEvent_t* ev = ring[0];
   double lastMs[5] = {0, 0, 0, 0, 0};
@@ -146,6 +147,7 @@ int qmgpu_create_ex(const qmgpu_problem* problem, int device, int max_batch, int
     HIP_CHECK(QM_ALLOW_DYNAMIC_LDS(wbc_kernel, WBC_LDS_BYTES));
     HIP_CHECK(prepareMpcKernels());
     HIP_CHECK(QM_ALLOW_DYNAMIC_LDS(value_function_kernel, VALUE_LDS_BYTES));
+    HIP_CHECK(QM_ALLOW_DYNAMIC_LDS(metrics_kernel, METRICS_LDS_BYTES));
     QM_LAUNCH(input_weight_kernel, 1, 64, ctx->stream, ctx->m.dP, ctx->m.dZeros, ctx->m.dRw);
     HIP_CHECK(hipGetLastError());
     if (dtype == QMGPU_F32) ctx->m32 = qmk32::create(*problem, max_batch, max_nodes, ctx->stream, ctx->rawAlloc);
@@ -317,9 +319,9 @@ static void enqueueWbc(qmgpu_handle h, const qmgpu_wbc_args* w, hipStream_t stre
 static void beginTiming(qmgpu_handle h) {
   if (h->timing) h->ev = h->ring[h->callCount % qmgpu_context::kRing];
 }
-static void finishTiming(qmgpu_handle h, bool mpc, bool wbc) {
+static void finishTiming(qmgpu_handle h, bool mpc, bool wbc, bool single = false) {
   if (!h->timing) return;
-  h->ringKind[h->callCount % qmgpu_context::kRing] = (mpc ? 1 : 0) | (wbc ? 2 : 0);
+  h->ringKind[h->callCount % qmgpu_context::kRing] = (mpc ? 1 : 0) | (wbc ? 2 : 0) | (single ? 4 : 0);
   ++h->callCount;
 }
 // elapsed times of one recorded call: [ad_node, lq_node, riccati, linesearch, wbc, whole]
@@ -327,6 +329,14 @@ static void readTiming(qmgpu_handle h, long call, double* ms6) {
   hipEvent_t* ev = h->ring[call % qmgpu_context::kRing];
   const int kind = h->ringKind[call % qmgpu_context::kRing];
   const bool mpc = kind & 1, wbc = kind & 2;
+  if (kind & 4) {   // a call of one launch: the whole call only
+    HIP_CHECK(hipEventSynchronize(ev[EV_LINE_SEARCH]));
+    float ms = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms, ev[EV_START], ev[EV_LINE_SEARCH]));
+    for (int i = 0; i < 6; ++i) ms6[i] = 0.0;
+    ms6[5] = double(ms);
+    return;
+  }
   const TimingEvent first = mpc ? EV_START : EV_WBC_START, last = wbc ? EV_WBC_END : EV_LINE_SEARCH;
   HIP_CHECK(hipEventSynchronize(ev[last]));
   auto elapsed = [&](TimingEvent from, TimingEvent to) { float ms = 0.f; HIP_CHECK(hipEventElapsedTime(&ms, ev[from], ev[to])); return double(ms); };
@@ -393,6 +403,27 @@ int qmgpu_mpc_dual_batch(qmgpu_handle h, int batch, int num_nodes, double* costa
     DualArgs da{batch, num_nodes, h->m.dStages, h->m.dGains, h->m.dDtgrid, h->m.dInstStats, h->m.ddX, h->m.ddU, nu ? h->m.dDebug : nullptr, h->m.dStageNc, costate, nu, nc, status};
     QM_LAUNCH_DYN(costate_kernel, batch, DUAL_THREADS, DUAL_LDS_BYTES, h->stream, da);
     if (nu || nc) QM_LAUNCH(dual_multiplier_kernel, batch * num_nodes, 64, h->stream, da);
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
+int qmgpu_mpc_metrics_batch(qmgpu_handle h, const qmgpu_metrics_args* a) {
+  if (!a) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null argument");
+  // reads the model, the settings and R' (nothing a solve or a pending WBC writes) plus the caller's arrays; writes the caller's outputs only
+  return onHandle(h, [&]() {
+    if (h->dtype != QMGPU_F64) throw std::invalid_argument("the solution metrics exist for QMGPU_F64 handles only");
+    if (a->batch < 1 || a->num_nodes < 1 || a->num_target_knots < 1) throw std::invalid_argument("batch, num_nodes and num_target_knots must be positive");
+    if (a->batch > h->maxBatch || a->num_nodes > h->maxNodes) throw std::invalid_argument("batch / num_nodes exceed the capacity given to qmgpu_create");
+    if (!a->time_grid || !a->X || !a->U) throw std::invalid_argument("missing trajectory pointer (time_grid, X, U)");
+    if (!a->target_times || !a->target_states || !a->sched_num_events || !a->sched_event_times || !a->sched_modes) throw std::invalid_argument("missing target or schedule pointer");
+    static_assert(sizeof(int) == sizeof(int32_t) && METRICS_TERMS == QMGPU_NCOST_TERMS && METRICS_PERF == QMGPU_NPERF, "nc words; the widths of cost_terms and performance");
+    MetricsArgs ma{h->m.dP, h->m.dRw, a->batch, a->num_nodes, a->num_target_knots, a->time_grid, a->X, a->U, a->x0, a->target_times, a->target_states, a->sched_num_events,
+                   a->sched_event_times, a->sched_modes, a->ee_contact_ref, a->node_cost, a->cost_terms, a->defect, a->eq, a->nc, a->performance};
+    beginTiming(h);
+    if (h->timing) HIP_CHECK(hipEventRecord(h->ev[EV_START], h->stream));
+    QM_LAUNCH_DYN(metrics_kernel, a->batch, METRICS_THREADS, METRICS_LDS_BYTES, h->stream, ma);
+    if (h->timing) HIP_CHECK(hipEventRecord(h->ev[EV_LINE_SEARCH], h->stream));
+    finishTiming(h, false, false, true);
     HIP_CHECK(hipGetLastError());
   });
 }
@@ -519,9 +550,18 @@ int qmgpu_kernel_ms_mean(qmgpu_handle h, int last_calls, double* ms6) {
   return onHandle(h, [&]() {
     if (!h->timing || h->callCount == 0) throw std::invalid_argument("no timed call recorded (qmgpu_enable_timing)");
     const long n = std::min<long>(std::min<long>(last_calls, h->callCount), qmgpu_context::kRing);
-    double acc[6] = {0, 0, 0, 0, 0, 0};
-    for (long c = h->callCount - n; c < h->callCount; ++c) { double m[6]; readTiming(h, c, m); for (int i = 0; i < 6; ++i) acc[i] += m[i]; }
-    for (int i = 0; i < 6; ++i) ms6[i] = acc[i] / double(n);
+    // a call of one launch (qmgpu_mpc_metrics_batch) is no MPC / WBC call: it stays out of the mean unless the window holds nothing else (then [5] is its mean)
+    double acc[6] = {0, 0, 0, 0, 0, 0}, single = 0.0;
+    long counted = 0;
+    for (long c = h->callCount - n; c < h->callCount; ++c) {
+      double m[6];
+      readTiming(h, c, m);
+      if (h->ringKind[c % qmgpu_context::kRing] & 4) { single += m[5]; continue; }
+      for (int i = 0; i < 6; ++i) acc[i] += m[i];
+      ++counted;
+    }
+    for (int i = 0; i < 6; ++i) ms6[i] = counted ? acc[i] / double(counted) : 0.0;
+    if (!counted) ms6[5] = single / double(n);
   });
 }
 

@@ -196,7 +196,7 @@ int qmgpu_synchronize(qmgpu_handle h);
  * are complete after qmgpu_synchronize, or on the handle's stream after qmgpu_join_wbc (a device-side wait, no host wait) -- NOT after the caller synchronises its own stream.
  * Which calls join by themselves: qmgpu_cycle_batch (before its policy evaluation), qmgpu_wbc_solve_batch, qmgpu_set_stream (the NEW stream waits), qmgpu_set_overlap,
  * qmgpu_update_settings, qmgpu_debug_poison, qmgpu_synchronize, qmgpu_destroy.  Which do NOT: qmgpu_mpc_solve_batch, qmgpu_policy_eval_batch, qmgpu_mpc_feedback_batch, qmgpu_policy_eval_feedback_batch,
- * qmgpu_mpc_value_function_batch, qmgpu_value_function_eval_batch, qmgpu_mpc_dual_batch, qmgpu_mpc_metrics_batch, qmgpu_frontend_batch, qmgpu_warm_start_batch, qmgpu_gait_schedule_batch, qmgpu_get_input_weight, qmgpu_pack_results -- they touch nothing the library owns that a pending WBC reads or writes, and run next to it.
+ * qmgpu_mpc_value_function_batch, qmgpu_value_function_eval_batch, qmgpu_mpc_dual_batch, qmgpu_mpc_metrics_batch, qmgpu_mpc_taskspace_batch, qmgpu_frontend_batch, qmgpu_warm_start_batch, qmgpu_gait_schedule_batch, qmgpu_get_input_weight, qmgpu_pack_results -- they touch nothing the library owns that a pending WBC reads or writes, and run next to it.
  * The pending WBC still READS the caller's rbd_measured / period / time (and ee_force) of that cycle and reads and writes input_last / working_set: those buffers must not
  * be modified -- by the caller's own kernels or copies on any stream, or through a non-joining call above -- until qmgpu_join_wbc, qmgpu_synchronize, or the next
  * qmgpu_cycle_batch / qmgpu_wbc_solve_batch has been issued on the handle. */
@@ -371,6 +371,52 @@ typedef struct qmgpu_metrics_args {
   double* performance;                 /* [batch][QMGPU_NPERF] */
 } qmgpu_metrics_args;
 int qmgpu_mpc_metrics_batch(qmgpu_handle h, const qmgpu_metrics_args* args);
+
+/* The planned trajectory in task space: what the consumers next to the solver read off a plan.  Replaces the host-side forward kinematics of upstream's QmVisualizer --
+ * publishOptimizedStateTrajectory (qm_interface/src/visualization/qm_visualization.cpp:90-189: the feet, CoM and end-effector lines over every state of the plan, and a
+ * "future foothold" wherever a foot lands, :158-181), publishObservation / publishCartesianMarkers (:267-317: foot positions, foot forces, centre of pressure) -- and
+ * the host kinematics a caller of qmgpu_frontend_args::feet_height needs.  Evaluated on ANY trajectory (time_grid, X, U): the outputs of a solve, a warm start, a
+ * rollout.  Every quantity is an output of the tree sweep the solve differentiates; all vectors are in world axes; foot index c is the contact order of U[3c..3c+2]
+ * and of qmgpu_model::foot_body.  With r_c, v_c the position (relative to the base origin) and joint-induced velocity of foot c, r_ee, R_ee the end-effector's, and
+ * dp, omega, com_rel the base velocity, angular velocity and centre of mass (relative to the base origin) of the centroidal model at (x_k, u_k):
+ *     feet_pos      x_k[6..8] + r_c                                               ee_pos   x_k[6..8] + r_ee
+ *     ee_quat       R_ee as a quaternion, x y z w, Eigen's Quaternion(Matrix3) sign rule (ocs2::matrixToQuaternion): the one the end-effector cost compares
+ *     com           x_k[6..8] + com_rel
+ *     feet_vel      dp + omega x r_c + v_c at (x_k, u_k), k < N: the foot velocity implied by the centroidal momentum and the joint rates -- the three values a stance
+ *                   foot contributes to eq of qmgpu_mpc_metrics_batch (with position_error_gain = 0)
+ *     base_twist    [dp ; omega], k < N: the base velocity WbcBase::updateDesired reconstructs from the plan (qm_wbc/src/WbcBase.cpp:205-238)
+ *     cop           k < N.  With fz_c = u_k[3c+2] and s = ((fz_0 + fz_1) + fz_2) + fz_3, added in this order: (sum_c fz_c feet_pos_c) / s if s > 0, else three zeros.
+ *                   The sum runs over all four feet.  This project's own statement of the centre-of-pressure marker upstream draws from the contact forces.
+ *     foothold_flag [e][c] = 1 where foot c lands at event e: e < sched_num_events, time_grid[0] < sched_event_times[e] < time_grid[N] (both strict, on the values as
+ *                   given), foot c not in contact in sched_modes[e] and in contact in sched_modes[e+1] (qm_visualization.cpp:163-175); 0 everywhere else
+ *     foothold_pos  [e][c] the position of foot c at the state interpolated linearly from X at sched_event_times[e] (index and weight of upstream's
+ *                   LinearInterpolation::timeSegment, as qmgpu_policy_eval_batch interpolates X) where foothold_flag[e][c] = 1; three zeros everywhere else
+ * Stateless: needs no previous solve, reads the model behind the handle plus these arrays, writes every entry of every non-NULL output (events e >= sched_num_events
+ * included) and leaves every later solve bit-identical.  An instance's outputs are the same bits alone and inside a larger batch.  All device pointers.  Enqueued on
+ * the handle's stream, no host synchronisation.  Does not join a WBC pending on the overlap stream.  Records nothing in the timing ring: qmgpu_last_kernel_ms,
+ * qmgpu_kernel_ms_mean and qmgpu_kernel_ms_history are the same before and after it.  QMGPU_ERR_INVALID_ARGUMENT: a QMGPU_F32 handle; batch or num_nodes below 1 or
+ * beyond the handle's capacity; time_grid or X missing; feet_vel, base_twist or cop requested with U == NULL; foothold_pos or foothold_flag requested without all three
+ * schedule arrays. */
+typedef struct qmgpu_taskspace_args {
+  int32_t batch, num_nodes;            /* N intervals -> N+1 nodes */
+  const double* time_grid;             /* [batch][N+1] */
+  const double* X;                     /* [batch][N+1][30] */
+  const double* U;                     /* [batch][N][30] or NULL */
+  const int32_t* sched_num_events;     /* as qmgpu_mpc_args, or all three NULL */
+  const double* sched_event_times;
+  const int32_t* sched_modes;
+  /* outputs: device pointers, each may be NULL */
+  double* feet_pos;                    /* [batch][N+1][4][3] */
+  double* ee_pos;                      /* [batch][N+1][3]    */
+  double* ee_quat;                     /* [batch][N+1][4]    */
+  double* com;                         /* [batch][N+1][3]    */
+  double* feet_vel;                    /* [batch][N][4][3]   needs U */
+  double* base_twist;                  /* [batch][N][6]      needs U */
+  double* cop;                         /* [batch][N][3]      needs U */
+  double* foothold_pos;                /* [batch][QMGPU_MAX_EVENTS][4][3]  needs the schedule */
+  int32_t* foothold_flag;              /* [batch][QMGPU_MAX_EVENTS][4]     needs the schedule */
+} qmgpu_taskspace_args;
+int qmgpu_mpc_taskspace_batch(qmgpu_handle h, const qmgpu_taskspace_args* args);
 
 /* Initial guess of the next MPC call from the previous solution: (X, U) of the previous grid resampled (linear interpolation, end values held, as
  * upstream's LinearInterpolation) on new_grid [batch][new_nodes + 1]; x[0] of each instance is overwritten with x0 when x0 != NULL.  The results

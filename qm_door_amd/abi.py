@@ -80,6 +80,15 @@ class MetricsArgs(C.Structure):
     ]
 
 
+class TaskspaceArgs(C.Structure):
+    _fields_ = [
+        ("batch", i32), ("num_nodes", i32),
+        ("time_grid", C.c_void_p), ("X", C.c_void_p), ("U", C.c_void_p), ("sched_num_events", C.c_void_p), ("sched_event_times", C.c_void_p), ("sched_modes", C.c_void_p),
+        ("feet_pos", C.c_void_p), ("ee_pos", C.c_void_p), ("ee_quat", C.c_void_p), ("com", C.c_void_p), ("feet_vel", C.c_void_p), ("base_twist", C.c_void_p), ("cop", C.c_void_p),
+        ("foothold_pos", C.c_void_p), ("foothold_flag", C.c_void_p),
+    ]
+
+
 class WbcArgs(C.Structure):
     _fields_ = [
         ("batch", i32), ("variant", i32),
@@ -109,7 +118,7 @@ F64, F32 = 0, 1   # qmgpu_dtype
 SYMBOLS = [
     "qmgpu_strerror", "qmgpu_last_error", "qmgpu_load_problem", "qmgpu_load_gait", "qmgpu_mode_from_string", "qmgpu_tile_gait", "qmgpu_switch_gait", "qmgpu_time_grid_with_events", "qmgpu_warm_start_batch",
     "qmgpu_create", "qmgpu_create_ex", "qmgpu_destroy", "qmgpu_set_stream", "qmgpu_synchronize", "qmgpu_get_input_weight", "qmgpu_mpc_solve_batch",
-    "qmgpu_policy_eval_batch", "qmgpu_mpc_feedback_batch", "qmgpu_policy_eval_feedback_batch", "qmgpu_mpc_value_function_batch", "qmgpu_value_function_eval_batch", "qmgpu_mpc_dual_batch", "qmgpu_mpc_metrics_batch", "qmgpu_frontend_batch", "qmgpu_wbc_solve_batch", "qmgpu_cycle_batch", "qmgpu_debug_get_lq", "qmgpu_last_kernel_ms",
+    "qmgpu_policy_eval_batch", "qmgpu_mpc_feedback_batch", "qmgpu_policy_eval_feedback_batch", "qmgpu_mpc_value_function_batch", "qmgpu_value_function_eval_batch", "qmgpu_mpc_dual_batch", "qmgpu_mpc_metrics_batch", "qmgpu_mpc_taskspace_batch", "qmgpu_frontend_batch", "qmgpu_wbc_solve_batch", "qmgpu_cycle_batch", "qmgpu_debug_get_lq", "qmgpu_last_kernel_ms",
     "qmgpu_set_overlap", "qmgpu_join_wbc", "qmgpu_enable_timing", "qmgpu_enable_debug", "qmgpu_debug_poison", "qmgpu_kernel_ms_mean", "qmgpu_kernel_ms_history", "qmgpu_pack_results", "qmgpu_update_settings", "qmgpu_gait_schedule_batch",
 ]
 
@@ -171,6 +180,7 @@ def load_library(path=None):
     lib.qmgpu_value_function_eval_batch.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
     lib.qmgpu_mpc_dual_batch.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
     lib.qmgpu_mpc_metrics_batch.argtypes = [C.c_void_p, C.POINTER(MetricsArgs)]
+    lib.qmgpu_mpc_taskspace_batch.argtypes = [C.c_void_p, C.POINTER(TaskspaceArgs)]
     lib.qmgpu_warm_start_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.qmgpu_wbc_solve_batch.argtypes = [C.c_void_p, C.POINTER(WbcArgs)]
     lib.qmgpu_cycle_batch.argtypes = [C.c_void_p, C.POINTER(MpcArgs), C.c_void_p, C.POINTER(WbcArgs)]

@@ -255,6 +255,28 @@ class GpuSolver:
         values of the state-input equalities with nc, and the PerformanceIndex of the trajectory in `args` (metrics_args).  Stateless: needs no previous solve."""
         abi.check(self.lib, self.lib.qmgpu_mpc_metrics_batch(self.handle, C.byref(args)))
 
+    @staticmethod
+    def taskspace_args(batch, num_nodes, time_grid, X, U=None, sched_num=None, sched_times=None, sched_modes=None, feet_pos=None, ee_pos=None, ee_quat=None, com=None,
+                       feet_vel=None, base_twist=None, cop=None, foothold_pos=None, foothold_flag=None):
+        """qmgpu_taskspace_args: the trajectory (time_grid [batch][N+1], X, optional U) and optionally the schedule as mpc_args; outputs, each optional, world axes, feet in
+        contact order: feet_pos [batch][N+1][4][3], ee_pos [batch][N+1][3], ee_quat [batch][N+1][4] (x y z w), com [batch][N+1][3]; with U: feet_vel [batch][N][4][3],
+        base_twist [batch][N][6], cop [batch][N][3]; with the schedule: foothold_pos [batch][MAX_EVENTS][4][3], foothold_flag [batch][MAX_EVENTS][4] int32"""
+        a = abi.TaskspaceArgs()
+        a.batch, a.num_nodes = batch, num_nodes
+        vals = (("time_grid", time_grid), ("X", X), ("U", U), ("sched_num_events", sched_num), ("sched_event_times", sched_times), ("sched_modes", sched_modes),
+                ("feet_pos", feet_pos), ("ee_pos", ee_pos), ("ee_quat", ee_quat), ("com", com), ("feet_vel", feet_vel), ("base_twist", base_twist), ("cop", cop),
+                ("foothold_pos", foothold_pos), ("foothold_flag", foothold_flag))
+        for name, val in vals:
+            setattr(a, name, _ptr(val))
+        a._keep = tuple(v for _, v in vals)
+        return a
+
+    def taskspace(self, args):
+        """The planned task-space trajectories (qmgpu_mpc_taskspace_batch; the forward kinematics of upstream's QmVisualizer::publishOptimizedStateTrajectory): foot, end-effector
+        and CoM positions per node, foot velocities, base twist and centre of pressure per intermediate node, and the footholds of the feet that land at the events of the
+        schedule, of the trajectory in `args` (taskspace_args).  Stateless: needs no previous solve."""
+        abi.check(self.lib, self.lib.qmgpu_mpc_taskspace_batch(self.handle, C.byref(args)))
+
     def pack_results(self, batch, num_nodes, X, U, wbc_out, modes, packed):
         """X | U | WBC output | modes of every instance into one row of `packed` [batch][sharding.pack_len(N)] on the handle's stream (qmgpu_pack_results): the all-gather record"""
         abi.check(self.lib, self.lib.qmgpu_pack_results(self.handle, batch, num_nodes, _ptr(X), _ptr(U), _ptr(wbc_out), _ptr(modes), _ptr(packed)))

@@ -21,6 +21,7 @@
 #include "kernels/value_kernel.h"
 #include "kernels/dual_kernel.h"
 #include "kernels/metrics_kernel.h"
+#include "kernels/taskspace_kernel.h"
 #include "kernels/wbc_kernel.h"
 #include "kernels/frontend_kernel.h"
 #include "mpc32.h"
@@ -148,6 +149,7 @@ int qmgpu_create_ex(const qmgpu_problem* problem, int device, int max_batch, int
     HIP_CHECK(prepareMpcKernels());
     HIP_CHECK(QM_ALLOW_DYNAMIC_LDS(value_function_kernel, VALUE_LDS_BYTES));
     HIP_CHECK(QM_ALLOW_DYNAMIC_LDS(metrics_kernel, METRICS_LDS_BYTES));
+    HIP_CHECK(QM_ALLOW_DYNAMIC_LDS(taskspace_kernel, TASKSPACE_LDS_BYTES));
     QM_LAUNCH(input_weight_kernel, 1, 64, ctx->stream, ctx->m.dP, ctx->m.dZeros, ctx->m.dRw);
     HIP_CHECK(hipGetLastError());
     if (dtype == QMGPU_F32) ctx->m32 = qmk32::create(*problem, max_batch, max_nodes, ctx->stream, ctx->rawAlloc);
@@ -424,6 +426,25 @@ int qmgpu_mpc_metrics_batch(qmgpu_handle h, const qmgpu_metrics_args* a) {
     QM_LAUNCH_DYN(metrics_kernel, a->batch, METRICS_THREADS, METRICS_LDS_BYTES, h->stream, ma);
     if (h->timing) HIP_CHECK(hipEventRecord(h->ev[EV_LINE_SEARCH], h->stream));
     finishTiming(h, false, false, true);
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
+int qmgpu_mpc_taskspace_batch(qmgpu_handle h, const qmgpu_taskspace_args* a) {
+  if (!a) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null argument");
+  // reads the model (nothing a solve or a pending WBC writes) plus the caller's arrays; writes the caller's outputs only.  Not timed: nothing enters the event ring
+  return onHandle(h, [&]() {
+    if (h->dtype != QMGPU_F64) throw std::invalid_argument("the task-space trajectories exist for QMGPU_F64 handles only");
+    if (a->batch < 1 || a->num_nodes < 1) throw std::invalid_argument("batch and num_nodes must be positive");
+    if (a->batch > h->maxBatch || a->num_nodes > h->maxNodes) throw std::invalid_argument("batch / num_nodes exceed the capacity given to qmgpu_create");
+    if (!a->time_grid || !a->X) throw std::invalid_argument("missing trajectory pointer (time_grid, X)");
+    if ((a->feet_vel || a->base_twist || a->cop) && !a->U) throw std::invalid_argument("feet_vel, base_twist and cop need U");
+    if ((a->foothold_pos || a->foothold_flag) && !(a->sched_num_events && a->sched_event_times && a->sched_modes))
+      throw std::invalid_argument("foothold_pos and foothold_flag need the schedule (sched_num_events, sched_event_times, sched_modes)");
+    static_assert(sizeof(int) == sizeof(int32_t), "schedule and flag words");
+    TaskspaceArgs ta{h->m.dP, a->batch, a->num_nodes, a->time_grid, a->X, a->U, a->sched_num_events, a->sched_event_times, a->sched_modes, a->feet_pos, a->ee_pos, a->ee_quat,
+                     a->com, a->feet_vel, a->base_twist, a->cop, a->foothold_pos, a->foothold_flag};
+    QM_LAUNCH_DYN(taskspace_kernel, a->batch, TASKSPACE_THREADS, TASKSPACE_LDS_BYTES, h->stream, ta);
     HIP_CHECK(hipGetLastError());
   });
 }

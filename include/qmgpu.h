@@ -456,6 +456,53 @@ int qmgpu_wbc_solve_batch(qmgpu_handle h, const qmgpu_wbc_args* args);
 /* One control cycle per robot: MPC solve, policy evaluation at t_eval, WBC.  */
 int qmgpu_cycle_batch(qmgpu_handle h, const qmgpu_mpc_args* mpc, const double* t_eval /*[batch]*/, qmgpu_wbc_args* wbc);
 
+/* The plant step: the robot the WBC's torques act on.  Advances every instance's 24-DoF rigid-body state -- the model the WBC evaluates -- by dt under a joint
+ * command held over the call, with the feet named by `mode` pinned to the ground.
+ * THE REFERENCE'S PART is the hybrid joint command law of QMHWSim::writeSim (qm_gazebo/src/QMHWSim.cpp:90-113),
+ *     tau_j = kp_j (pos_des_j - q_j) + kd_j (vel_des_j - dq_j) + tau_ff_j        (:112-113, the terms added in this order),
+ * with the command QMController::updateControlLaw sets per joint (qm_controllers/src/QMController.cpp:178-191: legs (posDes, velDes, 0, 3, torque) once t > 10 s,
+ * arm (posDes, 0, arm_kp_wbc_, arm_kd_wbc_, torque)); tau_ff is the tail out[36..53] of qmgpu_wbc_args::out.  With clamp_effort != 0 the torque is then clamped to
+ * the effort limits of the WBC's torque-limit task (the first leg's three limits for every leg, the arm's own).  Not restated: the command delay buffer (:100-111).
+ * EVERYTHING ELSE IS THIS PROJECT'S OWN FORMULATION: in the reference this place is taken by the simulator behind QMHWSim.  Coordinates are the WBC's,
+ * q = [p, zyx, q_j], v = dq/dt (Euler rates).  The call runs S = substeps steps of h = dt / S; each evaluates the joint law at the current (q, v), then
+ *     M(q), nle(q, v) with -J_ee' f_e folded in as the WBC does, Jc(q) = the rows of the feet Jacobian of the feet in contact by `mode`, in foot order,
+ *     M (v+ - v) / h + nle = S' tau + Jc' F,     Jc v+ = 0          (velocity-level time stepping, inelastic contacts, F bilateral),
+ *     q+ = q + h v+                                                 (semi-implicit Euler; angles are not wrapped),
+ * solved by M = L L', Y = L^-1 Jc', G = Y'Y, Cholesky of G (at most 12 x 12; none in flight, mode 0).  Between substeps the state passes through its rbd form, as
+ * between calls: S substeps are S calls of dt / S bit for bit, except contact_force and tau_applied, which are the last substep's.  After the last substep rbd_next holds the Euler angles,
+ * position and joints of q+, the world angular velocity of the Euler rates (the inverse of the map the WBC applies to rbd_measured), the linear and joint rates,
+ * and in slots 48..54 the end-effector position and quaternion (x y z w, the sign rule of qmgpu_taskspace_args::ee_quat) AT q+, as
+ * StateEstimateBase::updateArmEE fills them (qm_estimation/src/StateEstimateBase.cpp:89-102).
+ *     status  bit 0  a pivot of M or G was not positive, or a result is not finite: rbd_next is the INPUT state, contact_force and tau_applied are zero
+ *             bit 1  some stance foot pulls on the ground (F_z < 0) in some substep
+ *             bit 2  some stance foot's force lies outside the friction pyramid |F_x|, |F_y| <= mu F_z of settings.wbc_friction_coefficient in some substep
+ *             Bits 1 and 2 are reports, not interventions.
+ * What this is NOT: contacts come from the schedule, not from geometry; a pinned foot never slips; there is no ground, no penetration and no position-level
+ * stabilisation (a pinned foot drifts by O(h^2) per step); no command delay; no joint position limits.
+ * Stateless: reads the model and the settings behind the handle plus these arrays, writes every entry of every non-NULL output and leaves every later solve and WBC
+ * call bit-identical.  An instance's outputs are the same bits alone and inside a larger batch.  All device pointers; rbd_next may be rbd.  Enqueued on the handle's
+ * stream, no host synchronisation.  Does not join a WBC pending on the overlap stream.  Records nothing in the timing ring.  QMGPU_ERR_INVALID_ARGUMENT: a QMGPU_F32
+ * handle; batch below 1 or beyond the handle's capacity; substeps < 1; rbd, tau_ff, mode, dt or rbd_next missing; kp without pos_des, kd without vel_des. */
+typedef struct qmgpu_plant_args {
+  int32_t batch;
+  int32_t substeps;                    /* S >= 1: the call advances every robot by S steps of dt / S with the command held */
+  int32_t clamp_effort;                /* != 0: the joint torque is clamped to the effort limits the WBC's torque-limit task uses */
+  const double* rbd;                   /* [batch][55] state at t (layout of qmgpu_wbc_args::rbd_measured) */
+  const double* tau_ff;                /* [batch][18] feed-forward torque (the tail of qmgpu_wbc_args::out) */
+  const double* pos_des;               /* [batch][18] or NULL (then kp must be NULL) */
+  const double* vel_des;               /* [batch][18] or NULL (then kd must be NULL) */
+  const double* kp;                    /* [batch][18] or NULL -> 0 */
+  const double* kd;                    /* [batch][18] or NULL -> 0 */
+  const int32_t* mode;                 /* [batch] contact mode held during the call, 8 LF + 4 RF + 2 LH + RH */
+  const double* dt;                    /* [batch] > 0 */
+  const double* ee_force;              /* [batch][3] or NULL: as qmgpu_wbc_args::ee_force */
+  double* rbd_next;                    /* [batch][55] state at t + dt; may be the same pointer as rbd */
+  double* contact_force;               /* [batch][12] or NULL: F of the LAST substep, world axes, contact order of U[3c..3c+2]; swing feet zero */
+  double* tau_applied;                 /* [batch][18] or NULL: joint torque of the last substep after the law and the clamp */
+  int32_t* status;                     /* [batch] or NULL */
+} qmgpu_plant_args;
+int qmgpu_plant_step_batch(qmgpu_handle h, const qmgpu_plant_args* args);
+
 /* The solved batch as ONE record per instance, [batch][(N+1)*30 + N*30 + 54 + (N+1)] doubles = X | U | WBC output | contact modes (as doubles: exact): what the ranks of a
  * sharded batch all-gather (the path's only exchange; the collective itself is issued by the host through RCCL).  All device pointers; enqueued
  * on the handle's stream.  Does NOT join a WBC pending on the overlap stream (qmgpu_set_overlap): pack the buffers of a cycle whose WBC has been joined -- behind the

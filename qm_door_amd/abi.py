@@ -89,6 +89,15 @@ class TaskspaceArgs(C.Structure):
     ]
 
 
+class PlantArgs(C.Structure):
+    _fields_ = [
+        ("batch", i32), ("substeps", i32), ("clamp_effort", i32),
+        ("rbd", C.c_void_p), ("tau_ff", C.c_void_p), ("pos_des", C.c_void_p), ("vel_des", C.c_void_p), ("kp", C.c_void_p), ("kd", C.c_void_p),
+        ("mode", C.c_void_p), ("dt", C.c_void_p), ("ee_force", C.c_void_p),
+        ("rbd_next", C.c_void_p), ("contact_force", C.c_void_p), ("tau_applied", C.c_void_p), ("status", C.c_void_p),
+    ]
+
+
 class WbcArgs(C.Structure):
     _fields_ = [
         ("batch", i32), ("variant", i32),
@@ -118,7 +127,7 @@ F64, F32 = 0, 1   # qmgpu_dtype
 SYMBOLS = [
     "qmgpu_strerror", "qmgpu_last_error", "qmgpu_load_problem", "qmgpu_load_gait", "qmgpu_mode_from_string", "qmgpu_tile_gait", "qmgpu_switch_gait", "qmgpu_time_grid_with_events", "qmgpu_warm_start_batch",
     "qmgpu_create", "qmgpu_create_ex", "qmgpu_destroy", "qmgpu_set_stream", "qmgpu_synchronize", "qmgpu_get_input_weight", "qmgpu_mpc_solve_batch",
-    "qmgpu_policy_eval_batch", "qmgpu_mpc_feedback_batch", "qmgpu_policy_eval_feedback_batch", "qmgpu_mpc_value_function_batch", "qmgpu_value_function_eval_batch", "qmgpu_mpc_dual_batch", "qmgpu_mpc_metrics_batch", "qmgpu_mpc_taskspace_batch", "qmgpu_frontend_batch", "qmgpu_wbc_solve_batch", "qmgpu_cycle_batch", "qmgpu_debug_get_lq", "qmgpu_last_kernel_ms",
+    "qmgpu_policy_eval_batch", "qmgpu_mpc_feedback_batch", "qmgpu_policy_eval_feedback_batch", "qmgpu_mpc_value_function_batch", "qmgpu_value_function_eval_batch", "qmgpu_mpc_dual_batch", "qmgpu_mpc_metrics_batch", "qmgpu_mpc_taskspace_batch", "qmgpu_frontend_batch", "qmgpu_wbc_solve_batch", "qmgpu_plant_step_batch", "qmgpu_cycle_batch", "qmgpu_debug_get_lq", "qmgpu_last_kernel_ms",
     "qmgpu_set_overlap", "qmgpu_join_wbc", "qmgpu_enable_timing", "qmgpu_enable_debug", "qmgpu_debug_poison", "qmgpu_kernel_ms_mean", "qmgpu_kernel_ms_history", "qmgpu_pack_results", "qmgpu_update_settings", "qmgpu_gait_schedule_batch",
 ]
 
@@ -183,6 +192,7 @@ def load_library(path=None):
     lib.qmgpu_mpc_taskspace_batch.argtypes = [C.c_void_p, C.POINTER(TaskspaceArgs)]
     lib.qmgpu_warm_start_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.qmgpu_wbc_solve_batch.argtypes = [C.c_void_p, C.POINTER(WbcArgs)]
+    lib.qmgpu_plant_step_batch.argtypes = [C.c_void_p, C.POINTER(PlantArgs)]
     lib.qmgpu_cycle_batch.argtypes = [C.c_void_p, C.POINTER(MpcArgs), C.c_void_p, C.POINTER(WbcArgs)]
     lib.qmgpu_debug_get_lq.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.POINTER(i32)]
     lib.qmgpu_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(d)]

@@ -277,6 +277,26 @@ class GpuSolver:
         schedule, of the trajectory in `args` (taskspace_args).  Stateless: needs no previous solve."""
         abi.check(self.lib, self.lib.qmgpu_mpc_taskspace_batch(self.handle, C.byref(args)))
 
+    @staticmethod
+    def plant_args(batch, rbd, tau_ff, mode, dt, rbd_next, substeps=1, clamp_effort=False, pos_des=None, vel_des=None, kp=None, kd=None, ee_force=None,
+                   contact_force=None, tau_applied=None, status=None):
+        """qmgpu_plant_args: rbd [batch][55], tau_ff / pos_des / vel_des / kp / kd [batch][18] (the last four optional), mode [batch] int32, dt [batch], ee_force
+        [batch][3] or None; outputs rbd_next [batch][55] (may be rbd) and, each optional, contact_force [batch][12], tau_applied [batch][18], status [batch] int32"""
+        a = abi.PlantArgs()
+        a.batch, a.substeps, a.clamp_effort = batch, int(substeps), int(bool(clamp_effort))
+        vals = (("rbd", rbd), ("tau_ff", tau_ff), ("pos_des", pos_des), ("vel_des", vel_des), ("kp", kp), ("kd", kd), ("mode", mode), ("dt", dt), ("ee_force", ee_force),
+                ("rbd_next", rbd_next), ("contact_force", contact_force), ("tau_applied", tau_applied), ("status", status))
+        for name, val in vals:
+            setattr(a, name, _ptr(val))
+        a._keep = tuple(v for _, v in vals)
+        return a
+
+    def plant_step(self, args):
+        """The plant step (qmgpu_plant_step_batch; stands in for QMHWSim::writeSim and the simulator behind it): the hybrid joint law kp (pos_des - q) + kd (vel_des - dq) +
+        tau_ff and `substeps` steps of rigid-contact forward dynamics of the 24-DoF model with the feet of `mode` pinned, of the state and command in `args`
+        (plant_args).  Stateless: needs no previous solve."""
+        abi.check(self.lib, self.lib.qmgpu_plant_step_batch(self.handle, C.byref(args)))
+
     def pack_results(self, batch, num_nodes, X, U, wbc_out, modes, packed):
         """X | U | WBC output | modes of every instance into one row of `packed` [batch][sharding.pack_len(N)] on the handle's stream (qmgpu_pack_results): the all-gather record"""
         abi.check(self.lib, self.lib.qmgpu_pack_results(self.handle, batch, num_nodes, _ptr(X), _ptr(U), _ptr(wbc_out), _ptr(modes), _ptr(packed)))

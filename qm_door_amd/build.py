@@ -52,10 +52,14 @@ def device_units(extra_flags=()):
     # lq_node_kernel lives in a translation unit of its own (qmgpu_lq.hip) compiled at -O2: measured 2.7 % faster than at -O3 (0.456 -> 0.443 ms, profiles/r04i_variant_timing.txt),
     # bit-identical results; the profiling build keeps the single translation unit
     split_lq = not timing
+    # plant_kernel lives in a translation unit of its own (qmgpu_plant.hip says why), compiled as the rest; the profiling build keeps the single translation unit
+    split_plant = not timing
     units = {
-        "api": ("qmgpu_api.hip", [*hip_flags, *(["-DQM_LS_EXTERN"] if split_ls else []), *(["-DQM_LQ_EXTERN"] if split_lq else [])]),
+        "api": ("qmgpu_api.hip", [*hip_flags, *(["-DQM_LS_EXTERN"] if split_ls else []), *(["-DQM_LQ_EXTERN"] if split_lq else []), *(["-DQM_PLANT_EXTERN"] if split_plant else [])]),
         "mpc32": ("qmgpu_mpc32.hip", [*hip_flags, "-DQM_REAL=float", "-Dqmk=qmk32"]),
     }
+    if split_plant:
+        units["plant"] = ("qmgpu_plant.hip", [*hip_flags, "-Dqmk=qmkplant"])
     if split_ls:
         units["ls"] = ("qmgpu_ls.hip", [*base_flags, *extra_flags, "-mllvm", "-enable-ipra=1"])
     if split_lq:

@@ -24,6 +24,7 @@
 #include "kernels/taskspace_kernel.h"
 #include "kernels/wbc_kernel.h"
 #include "kernels/frontend_kernel.h"
+#include "kernels/plant_kernel.h"
 #include "mpc32.h"
 
 using namespace qmhost;
@@ -500,6 +501,23 @@ int qmgpu_wbc_solve_batch(qmgpu_handle h, const qmgpu_wbc_args* args) {
     enqueueWbc(h, args, h->stream);
     if (h->timing) HIP_CHECK(hipEventRecord(h->ev[EV_WBC_END], h->stream));
     finishTiming(h, false, true);
+  });
+}
+
+int qmgpu_plant_step_batch(qmgpu_handle h, const qmgpu_plant_args* a) {
+  if (!a) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null argument");
+  // reads the model and the settings (nothing a solve or a pending WBC writes) plus the caller's arrays; writes the caller's outputs only.  Not timed: nothing enters the event ring
+  return onHandle(h, [&]() {
+    if (h->dtype != QMGPU_F64) throw std::invalid_argument("the plant step exists for QMGPU_F64 handles only");
+    if (a->batch < 1 || a->batch > h->maxBatch) throw std::invalid_argument("batch outside the capacity given to qmgpu_create");
+    if (a->substeps < 1) throw std::invalid_argument("substeps must be at least 1");
+    if (!a->rbd || !a->tau_ff || !a->mode || !a->dt || !a->rbd_next) throw std::invalid_argument("missing plant pointer (rbd, tau_ff, mode, dt, rbd_next)");
+    if ((a->kp && !a->pos_des) || (a->kd && !a->vel_des)) throw std::invalid_argument("kp needs pos_des, kd needs vel_des");
+    static_assert(sizeof(int) == sizeof(int32_t), "mode and status words");
+    qmplant::PlantArgs pa{h->m.dP, a->batch, a->substeps, a->clamp_effort, a->rbd, a->tau_ff, a->pos_des, a->vel_des, a->kp, a->kd, a->mode, a->dt, a->ee_force,
+                          a->rbd_next, a->contact_force, a->tau_applied, a->status};
+    QM_LAUNCH_DYN(qmplant::plant_kernel, a->batch, PLANT_THREADS, PLANT_LDS_BYTES, h->stream, pa);
+    HIP_CHECK(hipGetLastError());
   });
 }
 

@@ -503,6 +503,86 @@ typedef struct qmgpu_plant_args {
 } qmgpu_plant_args;
 int qmgpu_plant_step_batch(qmgpu_handle h, const qmgpu_plant_args* args);
 
+/* The WBC solution report: what a decision vector x = [accelerations (24), contact forces (12)] does to every task of the whole-body controller -- which task is
+ * met, which torque or friction limit binds, how far an infeasible limit is exceeded -- and the torque it commands.  An EVALUATOR of any x, not a read-out of
+ * the solver: it rebuilds the model terms and the stacked tasks of the tick from the inputs of qmgpu_wbc_args, with the same device functions wbc_kernel runs, and forms
+ *     eq_residual[l] = A_l x - b_l     of the stacked equality task of level l = 0, 1, 2 (HierarchicalWbc.cpp:18-44 / HierarchicalMpcWbc.cpp:18-34), rows in the
+ *                                      order the builders are stacked, the swing-leg rows of level 1 with their weight of 100; rows >= r_l are zero;
+ *     ineq_margin    = f0 - D0 x       of the inequality rows of level 0: rows 0..17 tau_i <= limit_i, rows 18..35 -tau_i <= limit_i (torqueLimits), then five rows
+ *                                      of the friction pyramid per stance foot in foot order (-F_z, F_x - mu F_z, -F_x - mu F_z, F_y - mu F_z, -F_y - mu F_z <= 0),
+ *                                      then the 3 n_sw all-zero rows frictionCone keeps (margin exactly 0); m_0 = 36 + 5 n_st + 3 n_sw; rows >= m_0 are zero;
+ *     tau            = M_j a - J_j' F + nle_j      the torque WbcBase::updateCmd recovers from x (WbcBase.cpp:580-595), with -J_ee' f_e folded into nle as the
+ *                                      solve does; margin_i = limit_i - tau_i and margin_{18+i} = limit_i + tau_i;
+ *     rows           = r_0, r_1, r_2, m_0;
+ *     summary        [0..2] ||A_l x - b_l||_2 per level   [3..5] ||.||_inf per level   [6] minimum margin over the torque rows 0..35
+ *                    [7] minimum margin over the friction-pyramid rows, +inf when no foot is in stance
+ *                    [8] number of rows i < m_0 with margin_i <= active_tol (1 + |f0_i|)  (on or beyond the limit; the all-zero rows always count)
+ *                    [9] number of rows i < m_0 with margin_i < -active_tol (1 + |f0_i|)  (violated)
+ *                    [10] index of the row of minimum margin over all m_0 rows (the lowest such index)   [11] reserved, zero.
+ *                    Counts and indices are stored as doubles, which is exact.
+ * A negative margin is a violated row.  RELATION TO HoQp: the lower levels of the cascade keep the rows of a higher level hard up to the slack that level needed,
+ * D x <= f + v (HoQp.cpp:100-124), and hand the slacks on as HoQp::getStackedSlackSolutions (HoQp.h:29, filled at HoQp.cpp:152-158).  The slack is penalised alone
+ * (v' v / 2), so at the solution x of the level that owns the rows it is the amount by which a row is exceeded: max(0, -ineq_margin_i) evaluated at that x is the
+ * slack HoQp stacks for row i, and at the final x of the cascade max(0, -ineq_margin_i) is at most that slack.  The slacks and working
+ * sets as the solver held them are not returned (nothing is read out of wbc_kernel); qmgpu_wbc_report_layout slices the arrays into per-task pieces.
+ * input_last is the value inputLast_ had WHEN THE TICK WAS SOLVED: qmgpu_wbc_solve_batch overwrites qmgpu_wbc_args::input_last with input_desired
+ * (WbcBase.cpp:224-225), so a caller that wants the report of a solved tick copies input_last before the solve.  The report never writes it.  x is any vector: for a
+ * solved tick the head of qmgpu_wbc_args::out (x_stride 54) or a packed copy of it (x_stride 36).
+ * Stateless: reads the model and the settings behind the handle plus these arrays, writes every entry of every non-NULL output and leaves every later solve and WBC
+ * call bit-identical.  An instance's outputs are the same bits alone and inside a larger batch.  All device pointers.  Enqueued on the handle's stream, no host
+ * synchronisation.  Does not join a WBC pending on the overlap stream.  Records nothing in the timing ring.  QMGPU_ERR_INVALID_ARGUMENT: a QMGPU_F32 handle; batch
+ * below 1 or beyond the handle's capacity; state_desired, input_desired, rbd_measured, mode, period, time, input_last or x missing; variant outside {0, 1};
+ * x_stride outside {36, 54}. */
+enum { QMGPU_WBC_REPORT_LEVELS = 3, QMGPU_WBC_REPORT_EQ_ROWS = 22, QMGPU_WBC_REPORT_INEQ_ROWS = 56, QMGPU_WBC_REPORT_SUMMARY = 12 };
+typedef struct qmgpu_wbc_report_args {
+  int32_t batch;
+  int32_t variant;                     /* as qmgpu_wbc_args */
+  int32_t x_stride;                    /* doubles between the x of consecutive instances: 36 or 54 */
+  int32_t reserved;
+  const double* state_desired;         /* [batch][30] */
+  const double* input_desired;         /* [batch][30] */
+  const double* rbd_measured;          /* [batch][55] */
+  const int32_t* mode;                 /* [batch] */
+  const double* period;                /* [batch] */
+  const double* time;                  /* [batch] */
+  const double* ee_force;              /* [batch][3] or NULL */
+  const double* input_last;            /* [batch][30] inputLast_ as it was when the tick was solved; read only */
+  const double* x;                     /* [batch][x_stride], the first 36 of each read */
+  double active_tol;
+  /* outputs: device pointers, each may be NULL */
+  double* eq_residual;                 /* [batch][3][22] */
+  double* ineq_margin;                 /* [batch][56] */
+  double* tau;                         /* [batch][18] */
+  int32_t* rows;                       /* [batch][4] */
+  double* summary;                     /* [batch][12] */
+} qmgpu_wbc_report_args;
+int qmgpu_wbc_report_batch(qmgpu_handle h, const qmgpu_wbc_report_args* args);
+
+/* The row map of the report (host code, no device): for each of the 13 task builders of WbcBase, named after the reference's methods, where its rows lie.
+ * out13[k] describes builder k (its id is k): level -1 when the variant or task set does not use it (first_row and num_rows are then 0), else the level whose
+ * stacked task holds it; inequality != 0: its rows lie in ineq_margin, else in eq_residual[level]; first_row / num_rows inside that array (num_rows may be 0: a
+ * builder that is stacked with no rows, e.g. swingLeg with four feet in stance); weight: the factor it is stacked with (100 for swingLeg, else 1).
+ * frictionCone contributes two pieces: its inequality rows (the pyramid rows of the stance feet followed by the 3 n_sw all-zero rows) under QMGPU_WBC_TASK_FRICTION_CONE
+ * and the zero-force equality rows of the swing feet under QMGPU_WBC_TASK_SWING_ZERO_FORCE.  startup != 0 selects the start-up task set (time < 10 s,
+ * HierarchicalWbc.cpp:32-37; variant 1 has none).  rows4 (may be NULL) = r_0, r_1, r_2, m_0 as qmgpu_wbc_report_args::rows.  out13 may be NULL.
+ * QMGPU_ERR_INVALID_ARGUMENT: variant outside {0, 1}, mode outside 0..15. */
+typedef enum qmgpu_wbc_task_id {
+  QMGPU_WBC_TASK_FLOATING_BASE_EOM = 0, QMGPU_WBC_TASK_TORQUE_LIMITS = 1, QMGPU_WBC_TASK_NO_CONTACT_MOTION = 2, QMGPU_WBC_TASK_FRICTION_CONE = 3,
+  QMGPU_WBC_TASK_BASE_HEIGHT = 4, QMGPU_WBC_TASK_BASE_ANGULAR = 5, QMGPU_WBC_TASK_BASE_LINEAR = 6, QMGPU_WBC_TASK_EE_LINEAR = 7, QMGPU_WBC_TASK_EE_ANGULAR = 8,
+  QMGPU_WBC_TASK_SWING_LEG = 9, QMGPU_WBC_TASK_ARM_JOINT_NOMINAL_TRACKING = 10, QMGPU_WBC_TASK_CONTACT_FORCE = 11, QMGPU_WBC_TASK_SWING_ZERO_FORCE = 12,
+  QMGPU_WBC_NUM_TASKS = 13
+} qmgpu_wbc_task_id;
+typedef struct qmgpu_wbc_task_rows {
+  int32_t id;                          /* qmgpu_wbc_task_id */
+  int32_t level;                       /* 0..2, or -1: not used */
+  int32_t inequality;                  /* 0: rows of eq_residual[level]; 1: rows of ineq_margin */
+  int32_t first_row;
+  int32_t num_rows;
+  int32_t reserved;
+  double weight;
+} qmgpu_wbc_task_rows;
+int qmgpu_wbc_report_layout(int variant, int mode, int startup, qmgpu_wbc_task_rows* out13, int32_t* rows4);
+
 /* The solved batch as ONE record per instance, [batch][(N+1)*30 + N*30 + 54 + (N+1)] doubles = X | U | WBC output | contact modes (as doubles: exact): what the ranks of a
  * sharded batch all-gather (the path's only exchange; the collective itself is issued by the host through RCCL).  All device pointers; enqueued
  * on the handle's stream.  Does NOT join a WBC pending on the overlap stream (qmgpu_set_overlap): pack the buffers of a cycle whose WBC has been joined -- behind the

@@ -98,6 +98,25 @@ class PlantArgs(C.Structure):
     ]
 
 
+WBC_REPORT_LEVELS, WBC_REPORT_EQ_ROWS, WBC_REPORT_INEQ_ROWS, WBC_REPORT_SUMMARY = 3, 22, 56, 12
+# qmgpu_wbc_task_id: the task builders of WbcBase, and the zero-force rows of the swing feet as frictionCone stacks them
+WBC_TASKS = ("floatingBaseEom", "torqueLimits", "noContactMotion", "frictionCone", "baseHeight", "baseAngular", "baseLinear", "eeLinear", "eeAngular", "swingLeg",
+             "armJointNominalTracking", "contactForce", "swingZeroForce")
+
+
+class WbcReportArgs(C.Structure):
+    _fields_ = [
+        ("batch", i32), ("variant", i32), ("x_stride", i32), ("reserved", i32),
+        ("state_desired", C.c_void_p), ("input_desired", C.c_void_p), ("rbd_measured", C.c_void_p), ("mode", C.c_void_p), ("period", C.c_void_p), ("time", C.c_void_p),
+        ("ee_force", C.c_void_p), ("input_last", C.c_void_p), ("x", C.c_void_p), ("active_tol", d),
+        ("eq_residual", C.c_void_p), ("ineq_margin", C.c_void_p), ("tau", C.c_void_p), ("rows", C.c_void_p), ("summary", C.c_void_p),
+    ]
+
+
+class WbcTaskRows(C.Structure):
+    _fields_ = [("id", i32), ("level", i32), ("inequality", i32), ("first_row", i32), ("num_rows", i32), ("reserved", i32), ("weight", d)]
+
+
 class WbcArgs(C.Structure):
     _fields_ = [
         ("batch", i32), ("variant", i32),
@@ -127,7 +146,7 @@ F64, F32 = 0, 1   # qmgpu_dtype
 SYMBOLS = [
     "qmgpu_strerror", "qmgpu_last_error", "qmgpu_load_problem", "qmgpu_load_gait", "qmgpu_mode_from_string", "qmgpu_tile_gait", "qmgpu_switch_gait", "qmgpu_time_grid_with_events", "qmgpu_warm_start_batch",
     "qmgpu_create", "qmgpu_create_ex", "qmgpu_destroy", "qmgpu_set_stream", "qmgpu_synchronize", "qmgpu_get_input_weight", "qmgpu_mpc_solve_batch",
-    "qmgpu_policy_eval_batch", "qmgpu_mpc_feedback_batch", "qmgpu_policy_eval_feedback_batch", "qmgpu_mpc_value_function_batch", "qmgpu_value_function_eval_batch", "qmgpu_mpc_dual_batch", "qmgpu_mpc_metrics_batch", "qmgpu_mpc_taskspace_batch", "qmgpu_frontend_batch", "qmgpu_wbc_solve_batch", "qmgpu_plant_step_batch", "qmgpu_cycle_batch", "qmgpu_debug_get_lq", "qmgpu_last_kernel_ms",
+    "qmgpu_policy_eval_batch", "qmgpu_mpc_feedback_batch", "qmgpu_policy_eval_feedback_batch", "qmgpu_mpc_value_function_batch", "qmgpu_value_function_eval_batch", "qmgpu_mpc_dual_batch", "qmgpu_mpc_metrics_batch", "qmgpu_mpc_taskspace_batch", "qmgpu_frontend_batch", "qmgpu_wbc_solve_batch", "qmgpu_plant_step_batch", "qmgpu_wbc_report_batch", "qmgpu_wbc_report_layout", "qmgpu_cycle_batch", "qmgpu_debug_get_lq", "qmgpu_last_kernel_ms",
     "qmgpu_set_overlap", "qmgpu_join_wbc", "qmgpu_enable_timing", "qmgpu_enable_debug", "qmgpu_debug_poison", "qmgpu_kernel_ms_mean", "qmgpu_kernel_ms_history", "qmgpu_pack_results", "qmgpu_update_settings", "qmgpu_gait_schedule_batch",
 ]
 
@@ -193,6 +212,8 @@ def load_library(path=None):
     lib.qmgpu_warm_start_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.qmgpu_wbc_solve_batch.argtypes = [C.c_void_p, C.POINTER(WbcArgs)]
     lib.qmgpu_plant_step_batch.argtypes = [C.c_void_p, C.POINTER(PlantArgs)]
+    lib.qmgpu_wbc_report_batch.argtypes = [C.c_void_p, C.POINTER(WbcReportArgs)]
+    lib.qmgpu_wbc_report_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(WbcTaskRows), C.POINTER(i32)]
     lib.qmgpu_cycle_batch.argtypes = [C.c_void_p, C.POINTER(MpcArgs), C.c_void_p, C.POINTER(WbcArgs)]
     lib.qmgpu_debug_get_lq.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10 + [C.POINTER(i32)]
     lib.qmgpu_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(d)]

@@ -80,6 +80,16 @@ def time_grid_with_events(t0, tf, dt, event_times, max_nodes=1024, lib=None):
     return n.value, grid[:n.value + 1].copy()
 
 
+def wbc_report_layout(variant, mode, startup, lib=None):
+    """The row map of GpuSolver.wbc_report (qmgpu_wbc_report_layout, host code): ({builder name of abi.WBC_TASKS: dict(level, inequality, first_row, num_rows,
+    weight)}, [r_0, r_1, r_2, m_0]).  level -1: the variant / task set does not stack that builder; inequality: rows of ineq_margin, else of eq_residual[level]."""
+    lib = lib or abi.load_library()
+    t = (abi.WbcTaskRows * len(abi.WBC_TASKS))()
+    rows = (abi.i32 * 4)()
+    abi.check(lib, lib.qmgpu_wbc_report_layout(int(variant), int(mode), int(bool(startup)), t, rows))
+    return ({abi.WBC_TASKS[e.id]: dict(level=e.level, inequality=bool(e.inequality), first_row=e.first_row, num_rows=e.num_rows, weight=e.weight) for e in t}, list(rows))
+
+
 class GpuSolver:
     """Owns a qmgpu handle (device scratch + stream)."""
 
@@ -296,6 +306,29 @@ class GpuSolver:
         tau_ff and `substeps` steps of rigid-contact forward dynamics of the 24-DoF model with the feet of `mode` pinned, of the state and command in `args`
         (plant_args).  Stateless: needs no previous solve."""
         abi.check(self.lib, self.lib.qmgpu_plant_step_batch(self.handle, C.byref(args)))
+
+    @staticmethod
+    def wbc_report_args(batch, rbd, period, time, input_last, x, state_desired, input_desired, mode, variant=0, x_stride=None, ee_force=None, active_tol=1e-6,
+                        eq_residual=None, ineq_margin=None, tau=None, rows=None, summary=None):
+        """qmgpu_wbc_report_args: the inputs of a WBC tick as wbc_args (input_last: the value it had BEFORE that tick's solve, never written here) and the decision vector
+        x [batch][x_stride] to evaluate (x_stride 36, or 54 for the `out` of a solve; default: x's last dimension); outputs, each optional: eq_residual [batch][3][22],
+        ineq_margin [batch][56], tau [batch][18], rows [batch][4] int32, summary [batch][12]"""
+        a = abi.WbcReportArgs()
+        a.batch, a.variant, a.active_tol = batch, int(variant), float(active_tol)
+        a.x_stride = int(x.shape[-1]) if x_stride is None else int(x_stride)
+        vals = (("state_desired", state_desired), ("input_desired", input_desired), ("rbd_measured", rbd), ("mode", mode), ("period", period), ("time", time),
+                ("ee_force", ee_force), ("input_last", input_last), ("x", x), ("eq_residual", eq_residual), ("ineq_margin", ineq_margin), ("tau", tau), ("rows", rows),
+                ("summary", summary))
+        for name, val in vals:
+            setattr(a, name, _ptr(val))
+        a._keep = tuple(v for _, v in vals)
+        return a
+
+    def wbc_report(self, args):
+        """The WBC solution report (qmgpu_wbc_report_batch; what HoQp keeps next to its solution, HoQp::getStackedSlackSolutions): residual A_l x - b_l of every level's
+        stacked equality task, margin f0 - D0 x of the torque-limit and friction rows, the torque WbcBase::updateCmd recovers, and a summary, of the decision vector in
+        `args` (wbc_report_args).  Stateless: evaluates any x, needs no previous solve."""
+        abi.check(self.lib, self.lib.qmgpu_wbc_report_batch(self.handle, C.byref(args)))
 
     def pack_results(self, batch, num_nodes, X, U, wbc_out, modes, packed):
         """X | U | WBC output | modes of every instance into one row of `packed` [batch][sharding.pack_len(N)] on the handle's stream (qmgpu_pack_results): the all-gather record"""

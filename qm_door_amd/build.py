@@ -54,12 +54,17 @@ def device_units(extra_flags=()):
     split_lq = not timing
     # plant_kernel lives in a translation unit of its own (qmgpu_plant.hip says why), compiled as the rest; the profiling build keeps the single translation unit
     split_plant = not timing
+    # wbc_report_kernel likewise (qmgpu_wbcreport.hip): every existing unit but `api`, which gains the entry point, is built from the sources and flags it had
+    split_wbcreport = not timing
     units = {
-        "api": ("qmgpu_api.hip", [*hip_flags, *(["-DQM_LS_EXTERN"] if split_ls else []), *(["-DQM_LQ_EXTERN"] if split_lq else []), *(["-DQM_PLANT_EXTERN"] if split_plant else [])]),
+        "api": ("qmgpu_api.hip", [*hip_flags, *(["-DQM_LS_EXTERN"] if split_ls else []), *(["-DQM_LQ_EXTERN"] if split_lq else []), *(["-DQM_PLANT_EXTERN"] if split_plant else []),
+                                  *(["-DQM_WBCREPORT_EXTERN"] if split_wbcreport else [])]),
         "mpc32": ("qmgpu_mpc32.hip", [*hip_flags, "-DQM_REAL=float", "-Dqmk=qmk32"]),
     }
     if split_plant:
         units["plant"] = ("qmgpu_plant.hip", [*hip_flags, "-Dqmk=qmkplant"])
+    if split_wbcreport:
+        units["wbcreport"] = ("qmgpu_wbcreport.hip", [*hip_flags, "-Dqmk=qmkreport"])
     if split_ls:
         units["ls"] = ("qmgpu_ls.hip", [*base_flags, *extra_flags, "-mllvm", "-enable-ipra=1"])
     if split_lq:

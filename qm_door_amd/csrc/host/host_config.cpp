@@ -397,4 +397,38 @@ int qmgpu_time_grid_with_events(double t0, double tf, double dt, int32_t num_eve
   return QMGPU_OK;
 }
 
+// Where the rows of every task builder of WbcBase lie in the arrays of qmgpu_wbc_report_batch: the grouping of HierarchicalWbc::update (HierarchicalWbc.cpp:18-44,
+// variant 0) and HierarchicalMpcWbc::update (HierarchicalMpcWbc.cpp:18-34, variant 1) with Task::operator+ stacking the rows in the order the builders are added.
+int qmgpu_wbc_report_layout(int variant, int mode, int startup, qmgpu_wbc_task_rows* out13, int32_t* rows4) {
+  if ((variant != 0 && variant != 1) || mode < 0 || mode > 15) return setError(QMGPU_ERR_INVALID_ARGUMENT, "variant must be 0 or 1, mode 0..15");
+  int nst = 0;
+  for (int leg = 0; leg < 4; ++leg) nst += (mode >> (3 - leg)) & 1;
+  const int nsw = 4 - nst;
+  qmgpu_wbc_task_rows t[QMGPU_WBC_NUM_TASKS];
+  for (int k = 0; k < QMGPU_WBC_NUM_TASKS; ++k) t[k] = qmgpu_wbc_task_rows{k, -1, 0, 0, 0, 0, 1.0};
+  int r[3] = {0, 0, 0}, m0 = 0;
+  auto eq = [&](int id, int level, int count, double weight = 1.0) { t[id].level = level; t[id].first_row = r[level]; t[id].num_rows = count; t[id].weight = weight; r[level] += count; };
+  auto ineq = [&](int id, int count) { t[id].level = 0; t[id].inequality = 1; t[id].first_row = m0; t[id].num_rows = count; m0 += count; };
+  // level 0: floatingBaseEom + torqueLimits + noContactMotion + frictionCone
+  eq(QMGPU_WBC_TASK_FLOATING_BASE_EOM, 0, 6);
+  ineq(QMGPU_WBC_TASK_TORQUE_LIMITS, 2 * QMGPU_NJ);
+  eq(QMGPU_WBC_TASK_NO_CONTACT_MOTION, 0, 3 * nst);
+  eq(QMGPU_WBC_TASK_SWING_ZERO_FORCE, 0, 3 * nsw);
+  ineq(QMGPU_WBC_TASK_FRICTION_CONE, 5 * nst + 3 * nsw);
+  if (variant == 0 && startup) {
+    eq(QMGPU_WBC_TASK_ARM_JOINT_NOMINAL_TRACKING, 1, 6);
+  } else {
+    eq(QMGPU_WBC_TASK_BASE_HEIGHT, 1, 1);
+    eq(QMGPU_WBC_TASK_BASE_ANGULAR, 1, 3);
+    if (variant == 0) { eq(QMGPU_WBC_TASK_EE_LINEAR, 1, 3); eq(QMGPU_WBC_TASK_EE_ANGULAR, 1, 3); }
+    else eq(QMGPU_WBC_TASK_BASE_LINEAR, 1, 2);
+    eq(QMGPU_WBC_TASK_SWING_LEG, 1, 3 * nsw, 100.0);
+  }
+  eq(QMGPU_WBC_TASK_CONTACT_FORCE, 2, 12);
+  if (variant == 0) eq(QMGPU_WBC_TASK_BASE_LINEAR, 2, 2);
+  if (out13) for (int k = 0; k < QMGPU_WBC_NUM_TASKS; ++k) out13[k] = t[k];
+  if (rows4) { rows4[0] = r[0]; rows4[1] = r[1]; rows4[2] = r[2]; rows4[3] = m0; }
+  return QMGPU_OK;
+}
+
 }  // extern "C"

@@ -25,6 +25,7 @@
 #include "kernels/wbc_kernel.h"
 #include "kernels/frontend_kernel.h"
 #include "kernels/plant_kernel.h"
+#include "kernels/wbc_report_kernel.h"
 #include "mpc32.h"
 
 using namespace qmhost;
@@ -517,6 +518,24 @@ int qmgpu_plant_step_batch(qmgpu_handle h, const qmgpu_plant_args* a) {
     qmplant::PlantArgs pa{h->m.dP, a->batch, a->substeps, a->clamp_effort, a->rbd, a->tau_ff, a->pos_des, a->vel_des, a->kp, a->kd, a->mode, a->dt, a->ee_force,
                           a->rbd_next, a->contact_force, a->tau_applied, a->status};
     QM_LAUNCH_DYN(qmplant::plant_kernel, a->batch, PLANT_THREADS, PLANT_LDS_BYTES, h->stream, pa);
+    HIP_CHECK(hipGetLastError());
+  });
+}
+
+int qmgpu_wbc_report_batch(qmgpu_handle h, const qmgpu_wbc_report_args* a) {
+  if (!a) return setError(QMGPU_ERR_INVALID_ARGUMENT, "null argument");
+  // reads the model and the settings (nothing a solve or a pending WBC writes) plus the caller's arrays; writes the caller's outputs only.  Not timed: nothing enters the event ring
+  return onHandle(h, [&]() {
+    if (h->dtype != QMGPU_F64) throw std::invalid_argument("the WBC report exists for QMGPU_F64 handles only");
+    if (a->batch < 1 || a->batch > h->maxBatch) throw std::invalid_argument("batch outside the capacity given to qmgpu_create");
+    if (a->variant != 0 && a->variant != 1) throw std::invalid_argument("variant must be 0 (HierarchicalWbc) or 1 (HierarchicalMpcWbc)");
+    if (a->x_stride != QMGPU_NWBC_DEC && a->x_stride != QMGPU_NWBC_OUT) throw std::invalid_argument("x_stride must be 36 or 54");
+    if (!a->state_desired || !a->input_desired || !a->rbd_measured || !a->mode || !a->period || !a->time || !a->input_last || !a->x)
+      throw std::invalid_argument("missing report pointer (state_desired, input_desired, rbd_measured, mode, period, time, input_last, x)");
+    static_assert(sizeof(int) == sizeof(int32_t), "mode and rows words");
+    qmwbcreport::ReportArgs ra{h->m.dP, a->batch, a->variant, a->x_stride, a->state_desired, a->input_desired, a->rbd_measured, a->mode, a->period, a->time, a->ee_force,
+                               a->input_last, a->x, a->active_tol, a->eq_residual, a->ineq_margin, a->tau, a->rows, a->summary};
+    QM_LAUNCH_DYN(qmwbcreport::wbc_report_kernel, a->batch, WBCREPORT_THREADS, WBCREPORT_LDS_BYTES, h->stream, ra);
     HIP_CHECK(hipGetLastError());
   });
 }
